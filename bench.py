@@ -1,8 +1,13 @@
 """Headline benchmark: agent-steps/sec, gym_flock_v2 (periodic) 256 agents x 4096 envs per MI355X (BASELINE config 3).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config {2,3,4,5}]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config {2,3,4,5}] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
+
+A plain run does what the headline figure needs and no more: set up, W warmup steps, K timed steps, the outputs of the
+last timed step written to DIR (--dump-outputs), one JSON line (metric, value, unit, ms_per_step, ...). --full adds
+every other measurement to that line: the env kernel's roofline block (HIP events inside the timed region and the env
+step alone after it), the host enqueue cost per step, the actor-driven policy loop and the CPU baseline.
 
 One process per GPU. Envs are independent, so each rank steps its own 4096 envs with no data-path collective
 (weak scaling); the only collectives are the barrier around the timed region and the max-over-ranks of its time.
@@ -12,7 +17,14 @@ shared-critic replay ring inside that same launch and runs one learn() (B=256); 
 transition and run VDN / RNN-MADDPG train() every 150 / 250 steps. Inputs (state, a pool of synthetic actions)
 are resident in HBM before the timed region starts; the first update (graph capture) happens before it.
 
-Rank 0 prints ONE JSON line. Extra fields:
+Rank 0 prints ONE JSON line. --dump-outputs DIR: rank 0 also writes what the last timed step left its caller as
+DIR/<name>.npy (float32): the step's return values (obs, reward, done, any_done), the env state behind them (positions,
+headings, velocities for flock, nn_idx where tracked) and the learner's parameters, targets and losses. The inputs are
+seeded, so two runs with the same arguments write the same steps' outputs. At most 60 MB in all: when the arrays hold
+more, the large ones are cut to an equal number of elements, drawn at fixed seeded flat indices ("outputs" in the line
+names each array's shape and how many elements were kept).
+
+Extra fields with --full:
   roofline      the env step kernel (the dominant kernel), timed with HIP events on its launch stream.
                 HBM side: achieved = algorithmic bytes per agent-step (v2 93, uw 149,
                 uw_discrete 69) x agent-steps per launch / kernel time, frac = achieved / 8 TB/s; the fused replay
@@ -119,8 +131,16 @@ def parse():
                          "(default); 4 uw_discrete 512x8192 (global, split over the ranks) + VDN every 150 steps; "
                          "5 v2 1024x16384 (global) + RNN-MADDPG every 250 steps. --envs/--agents/--variant/--learner "
                          "override it")
-    ap.add_argument("--cpu-seconds", type=float, default=10.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the roofline block (HIP events around every "
+                         "EV_EVERY-th env step of the timed region, the env step alone), the host enqueue cost, the "
+                         "policy loop (--policy-steps) and the CPU baseline (--cpu-seconds, --no-cpu-baseline)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the last timed step's outputs (env step results and state, "
+                         "learner parameters) as DIR/<name>.npy, float32, at most 60 MB in all (large arrays: a fixed "
+                         "seeded sample)")
+    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="--full: length of the CPU baseline sample")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--pmc", default=None, help="JSON with measured HBM bytes per launch (profiles/)")
     ap.add_argument("--step-launches", type=int, default=None,
                     help="env step as this many launches over env ranges (FlockConfig.step_launches; default: 3 "
@@ -131,7 +151,7 @@ def parse():
                          "ScTrainLoop, K steps per C++ call (bitwise the per-step path); 0: one Python call per step "
                          "(flock::step_v2_store + the native learn() pipeline)")
     ap.add_argument("--policy-steps", type=int, default=20,
-                    help="config 3, N=1: also time this many steps of the actor-driven loop of the reference's "
+                    help="--full, config 3, N=1: also time this many steps of the actor-driven loop of the reference's "
                          "driver (choose_action of every agent + OU noise -> env.step + insert -> learn(), "
                          "learners/maddpg_shared_critic/train_flock.py:114-121) after the headline, reported in the "
                          "policy_in_loop field (0: skip)")
@@ -370,6 +390,63 @@ def valu_fields(vp, busy, lane_ops, kern_s, alone_ms, tag):
     return out
 
 
+def roofline_block(args, E, N, k, R, use_rollout, periodic, launches, kern_ms, alone_ms):
+    """The line's roofline field (--full): the env step's HIP-event time inside the timed region (kern_ms) and alone
+    (alone_ms) against the HBM and VALU rooflines, with the PMC summaries under profiles/."""
+    fused_ring = args.learner in RING_BYTES_PER_AGENT_STEP
+    bpa = BYTES_PER_AGENT_STEP[args.variant]
+    ins = RING_BYTES_PER_AGENT_STEP.get(args.learner, 0)
+    kern_s = kern_ms * 1e-3
+    achieved = bpa * E * N / kern_s / 1e9
+    tag = f"{args.variant}{'_ring' if fused_ring else ''}{'_rollout' if use_rollout else ''}_N{N}_E{E}"
+    prof = os.path.join(os.path.dirname(os.path.abspath(__file__)), "profiles")
+
+    def pmc(name):
+        path = os.path.join(prof, name)
+        if not os.path.exists(path):
+            return None
+        with open(path) as f:
+            return json.load(f)
+
+    pt = pmc(os.path.basename(args.pmc)) if args.pmc else pmc(f"pmc_{tag}.json")
+    traffic = pt.get("hbm_bytes_per_launch") if pt else None
+    if traffic is not None and use_rollout:  # per step, like achieved: the PMC pass's launches ran R steps each
+        traffic = traffic / pt.get("steps_per_launch", R)
+    vp = pmc(f"pmc_valu_{tag}.json")
+    valu = None
+    if vp and "SQ_ACTIVE_INST_VALU2" in vp:
+        busy = 4.0 * (vp["SQ_ACTIVE_INST_VALU"] - vp["SQ_ACTIVE_INST_VALU2"]) / SIMDS  # VALU issue cycles per SIMD
+        lane_ops = 64.0 * vp["SQ_INSTS_VALU"]
+        valu = valu_fields(vp, busy, lane_ops, kern_s, alone_ms, tag)
+    hbm_frac = achieved / HBM_PEAK_GBS
+    return {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+            "frac": hbm_frac, "traffic": traffic,
+            "kernel": (f"rollout_uw_kernel ({R} steps per launch, env state on chip)" if use_rollout
+                       and N == 64 and k == 4 else
+                       f"step_kernel<{k + 2},{'periodic' if periodic else 'euclidean'}"
+                       f"{',cells' if N >= 128 else ''}>" + (" + fused replay insert" if fused_ring else "")),
+            "kernel_ms": kern_ms, "bytes_per_agent_step": bpa,
+            **({"rollout_steps_per_launch": R,
+                "moved_bytes_per_agent_step": ROLLOUT_MOVED_BYTES} if use_rollout else {}),
+            "insert_bytes_per_agent_step": ins,
+            "achieved_incl_insert": (bpa + ins) * E * N / kern_s / 1e9,
+            "valu": valu,
+            "binding": binding(valu, hbm_frac, alone_ms, bpa * E * N),
+            "step_launches": launches,
+            # compare with rocprofv3's per-dispatch average
+            "kernel_ms_per_launch": kern_ms * R if use_rollout else kern_ms / launches,
+            "kernel_alone_ms": alone_ms,
+            "frac_alone": (bpa * E * N / (alone_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if alone_ms else None,
+            "valu_frac_alone": valu["frac_alone"] if valu else None,
+            "note": ("kernel_ms / frac: HIP events around every rollout launch of the timed region, per "
+                     "step; frac on SURVEY 8(d)'s 149-B accounting (a single step reads and rewrites the "
+                     "state and the memory); the rollout moves the action read and the observation / "
+                     "reward / done writes (moved_bytes_per_agent_step)" if use_rollout else
+                     f"kernel_ms / frac / valu: HIP events around every {EV_EVERY}th env step of the timed "
+                     "region (the step's launches, with the learner's kernels beside them); *_alone: the same "
+                     "step as one launch with no learner, after the timed region")}
+
+
 class VDNBench:
     """BASELINE config 4 learner: every env's team transition (obs, action ids, rewards, next obs, any_done) is put
     into the VDN replay ring each vectorized step (learners/vdn/train_flock.py:88-104), and VDN train() (10 updates
@@ -532,6 +609,63 @@ def cu_split_streams(dev, keep):
     return masked(lb), masked([i for i in range(ncu) if i not in set(lb)])
 
 
+DUMP_BUDGET_BYTES = 60 * 10**6   # --dump-outputs: all files together (float32)
+
+
+def step_outputs(env, hook):
+    """What the last step left its caller, by name: the values env.step() / env.rollout() return (the env holds the
+    last step's), the env state behind them, and what the learner's update wrote (parameters, targets, losses)."""
+    out = {"obs": env.obs_memory if env.obs_memory is not None else env.dnn, "reward": env.reward, "done": env.done,
+           "any_done": env.any_done, "positions": env.positions}
+    if env.cfg.variant == "flock":
+        out["velocities"] = env.velocities
+    else:
+        out["headings"] = env.headings
+    if env.nn_idx is not None:
+        out["nn_idx"] = env.nn_idx
+    L = getattr(hook, "learner", None)
+    if L is not None:
+        nets = {"critic": getattr(L, "critic", None), "critics": getattr(L, "critics", None),
+                "actors": getattr(L, "actors", None), "q": getattr(getattr(L, "q", None), "P", None)}
+        for name, fp in nets.items():
+            if fp is None:
+                continue
+            out[f"learner_{name}"] = fp.data
+            if fp.target is not None:
+                out[f"learner_{name}_target"] = fp.target
+        for name in ("losses", "loss"):
+            if isinstance(getattr(L, name, None), torch.Tensor):
+                out[f"learner_{name}"] = getattr(L, name)
+    return out
+
+
+def dump_outputs(path, arrays):
+    """arrays (name -> device tensor) as path/<name>.npy in float32, DUMP_BUDGET_BYTES at the most: the largest
+    element count `cap` with sum(min(numel, cap)) inside the budget; an array above it keeps `cap` elements at flat
+    indices drawn once from a fixed seed (sorted, the same for every run of the same shapes). Returns the manifest."""
+    os.makedirs(path, exist_ok=True)
+    sizes = sorted(t.numel() for t in arrays.values())
+    left, cap = DUMP_BUDGET_BYTES // 4, None
+    for i, n in enumerate(sizes):  # water-filling over the ascending sizes
+        if n * (len(sizes) - i) > left:
+            cap = left // (len(sizes) - i)
+            break
+        left -= n
+    rng = np.random.default_rng(20240607)
+    manifest = {}
+    for name, t in arrays.items():
+        flat = t.detach().reshape(-1)
+        kept = None
+        if cap is not None and flat.numel() > cap:
+            idx = np.sort(rng.integers(0, flat.numel(), size=cap))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+            kept = cap
+        a = flat.to(torch.float32).cpu().numpy()
+        np.save(os.path.join(path, name + ".npy"), a if kept is not None else a.reshape(tuple(t.shape)))
+        manifest[name] = {"shape": list(t.shape), "dtype": str(t.dtype).replace("torch.", ""), "sampled": kept}
+    return manifest
+
+
 def main():
     args = parse()
     world, rank, dev = setup_dist(args)
@@ -634,8 +768,9 @@ def main():
         hook.prime()  # graph capture / first update outside the timed region
     torch.cuda.synchronize(dev)
     # the env kernel's HIP-event timing: every EV_EVERY-th step of the timed region (two timing markers per step
-    # would add host and queue work of their own to a ~13-us launch-bound step)
-    ev = {s: (DevEvent(), DevEvent()) for s in range(0, args.steps, R if use_rollout else EV_EVERY)}
+    # would add host and queue work of their own to a ~13-us launch-bound step); --full only: the roofline block's
+    ev = {s: (DevEvent(), DevEvent()) for s in range(0, args.steps if args.full else 0,
+                                                     R if use_rollout else EV_EVERY)}
     evs = [e for s in sorted(ev) for e in ev[s]]
     for e in evs:  # create the HIP events outside the timed region
         e.record(stream)
@@ -678,14 +813,18 @@ def main():
         t = torch.tensor([el], dtype=torch.float64, device=dev)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         el = float(t.item())
-    if use_rollout:  # per step: each timed rollout call over the steps it ran
+    dumped = None
+    if args.dump_outputs and rank == 0:  # the last timed step's outputs, before anything else steps the env
+        dumped = dump_outputs(args.dump_outputs, step_outputs(env, hook))
+    kern_ms = None
+    if args.full and use_rollout:  # per step: each timed rollout call over the steps it ran
         kern_ms = float(np.mean([a.elapsed_time(b) / min(R, args.steps - s) for s, (a, b) in ev.items()]))
-    else:
+    elif args.full:
         kern_ms = float(np.mean([a.elapsed_time(b) for a, b in ev.values()]))
     # the env step alone (after the timed region, no learner beside it, as ONE launch): what the kernel does when it
     # has the GPU to itself
     alone_ms = None
-    if hook is not None:
+    if args.full and hook is not None:
         env.set_param("step_launches", 1)
         ev_alone = [(DevEvent(), DevEvent()) for _ in range(10)]
         for i, (a0, a1) in enumerate(ev_alone):
@@ -701,7 +840,7 @@ def main():
     # stream while 32 steps are enqueued, so no full hardware queue throttles the enqueue (in the timed region the
     # host runs ahead until the queue is full, and host_ms_per_step then follows the GPU)
     host_us = None
-    if use_loop:
+    if args.full and use_loop:
         hook.finish()
         torch.cuda.synchronize(dev)
         torch.cuda._sleep(int(2.4e9 * 0.05))
@@ -713,32 +852,6 @@ def main():
 
     total_agent_steps = world * E * N * args.steps
     value = total_agent_steps / el
-    fused_ring = args.learner in RING_BYTES_PER_AGENT_STEP
-    bpa = BYTES_PER_AGENT_STEP[args.variant]
-    ins = RING_BYTES_PER_AGENT_STEP.get(args.learner, 0)
-    kern_s = kern_ms * 1e-3
-    achieved = bpa * E * N / kern_s / 1e9
-    tag = f"{args.variant}{'_ring' if fused_ring else ''}{'_rollout' if use_rollout else ''}_N{N}_E{E}"
-    prof = os.path.join(os.path.dirname(os.path.abspath(__file__)), "profiles")
-
-    def pmc(name):
-        path = os.path.join(prof, name)
-        if not os.path.exists(path):
-            return None
-        with open(path) as f:
-            return json.load(f)
-
-    pt = pmc(os.path.basename(args.pmc)) if args.pmc else pmc(f"pmc_{tag}.json")
-    traffic = pt.get("hbm_bytes_per_launch") if pt else None
-    if traffic is not None and use_rollout:  # per step, like achieved: the PMC pass's launches ran R steps each
-        traffic = traffic / pt.get("steps_per_launch", R)
-    vp = pmc(f"pmc_valu_{tag}.json")
-    valu = None
-    if vp and "SQ_ACTIVE_INST_VALU2" in vp:
-        busy = 4.0 * (vp["SQ_ACTIVE_INST_VALU"] - vp["SQ_ACTIVE_INST_VALU2"]) / SIMDS  # VALU issue cycles per SIMD
-        lane_ops = 64.0 * vp["SQ_INSTS_VALU"]
-        valu = valu_fields(vp, busy, lane_ops, kern_s, alone_ms, tag)
-    hbm_frac = achieved / HBM_PEAK_GBS
     periodic = cfg.resolved().periodic
     c = CONFIGS[args.config]
     is_config = (args.variant, N, args.learner) == (c["variant"], c["agents"], c["learner"]) and (
@@ -764,7 +877,7 @@ def main():
         **({"diag_prewarm_ms": args.diag_prewarm_ms} if args.diag_prewarm_ms > 0 else {}),
         **({"diag_knobs": args.diag_knob} if args.diag_knob else {}),
         **({"diag_cu_split": args.diag_cu_split} if args.diag_cu_split else {}),
-        "host_enqueue_us_per_step": host_us,
+        **({"host_enqueue_us_per_step": host_us} if args.full else {}),
         "host_path": ("torch.classes.flock.ScTrainLoop: all timed steps in one C++ call" if use_loop else
                       f"VecFlockEnv.rollout: {R} steps per call (torch.ops.flock.rollout_uw)" if use_rollout else
                       "one Python step per vectorized step (torch.ops.flock)"),
@@ -780,39 +893,15 @@ def main():
             "learner": ("none: env step only" if hook is None else hook.describe()),
             "parallelism": f"env-shard x{world}",
         },
-        "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": hbm_frac, "traffic": traffic,
-                     "kernel": (f"rollout_uw_kernel ({R} steps per launch, env state on chip)" if use_rollout
-                                and N == 64 and k == 4 else
-                                f"step_kernel<{k + 2},{'periodic' if periodic else 'euclidean'}"
-                                f"{',cells' if N >= 128 else ''}>" + (" + fused replay insert" if fused_ring else "")),
-                     "kernel_ms": kern_ms, "bytes_per_agent_step": bpa,
-                     **({"rollout_steps_per_launch": R,
-                         "moved_bytes_per_agent_step": ROLLOUT_MOVED_BYTES} if use_rollout else {}),
-                     "insert_bytes_per_agent_step": ins,
-                     "achieved_incl_insert": (bpa + ins) * E * N / kern_s / 1e9,
-                     "valu": valu,
-                     "binding": binding(valu, hbm_frac, alone_ms, bpa * E * N),
-                     "step_launches": launches,
-                     # compare with rocprofv3's per-dispatch average
-                     "kernel_ms_per_launch": kern_ms * R if use_rollout else kern_ms / launches,
-                     "kernel_alone_ms": alone_ms,
-                     "frac_alone": (bpa * E * N / (alone_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if alone_ms else None,
-                     "valu_frac_alone": valu["frac_alone"] if valu else None,
-                     "note": ("kernel_ms / frac: HIP events around every rollout launch of the timed region, per "
-                              "step; frac on SURVEY 8(d)'s 149-B accounting (a single step reads and rewrites the "
-                              "state and the memory); the rollout moves the action read and the observation / "
-                              "reward / done writes (moved_bytes_per_agent_step)" if use_rollout else
-                              f"kernel_ms / frac / valu: HIP events around every {EV_EVERY}th env step of the timed "
-                              "region (the "
-                              "step's launches, with the learner's kernels beside them); *_alone: the same step as one "
-                              "launch with no learner, after the timed region")},
+        **({"outputs": {"dir": args.dump_outputs, "arrays": dumped}} if dumped is not None else {}),
     }
-    if (hook is not None and args.learner == "shared_critic" and world == 1 and args.policy_steps > 0
+    if args.full:
+        line["roofline"] = roofline_block(args, E, N, k, R, use_rollout, periodic, launches, kern_ms, alone_ms)
+    if (args.full and hook is not None and args.learner == "shared_critic" and world == 1 and args.policy_steps > 0
             and args.variant == "v2"):
         hook.finish()
         line["policy_in_loop"] = policy_loop(hook, env, args.warmup + args.steps + 100, args.policy_steps)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         line["cpu_baseline"] = cpu_baseline(args, box, args.cpu_seconds)
     if rank == 0:
         print(json.dumps(line), flush=True)

@@ -28,16 +28,16 @@ def _import(path, *mods):
         sys.path.remove(path)
 
 
-def test_main_py_loop_with_maddpg_rnn(cuda):
+def test_main_py_loop_with_maddpg_rnn(tmp_path, cuda):
     (gym_flock_v2,) = _import(ENVS, "gym_flock_v2")
     (MADDPG,) = _import(os.path.join(COMPAT, "maddpg_official_rnn"), "MADDPG")
     args = types.SimpleNamespace(nb_agents=10, k=4, collision_distance=2.5, normalize_distance=False,
                                  range_start=(0, 50), sensor_range=14, max_games=6, max_steps=40, ou_theta=0.15,
                                  ou_sigma=0.2, ou_sigma_min=0.001, ou_mu=0, ou_dt=0.01, batch_size=16,
                                  buffer_size=2000, min_size_buffer=60, gamma=0.99, tau=0.001,
-                                 save_dir=os.path.join(os.environ.get("TMPDIR", "/tmp"), "flock_ckpt"))
+                                 save_dir=str(tmp_path / "flock_ckpt"))
     env = gym_flock_v2.make_env(args)
-    super_agent = MADDPG.SuperAgent(args, env)
+    super_agent = MADDPG.SuperAgent(args, env, path_save=str(tmp_path), path_load=str(tmp_path))
     critic0 = super_agent.learner.critics.data.clone()
     trained = 0
     for n_game in range(args.max_games):  # main.py:24-59

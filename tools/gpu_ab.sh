@@ -3,7 +3,7 @@
 set -e
 for r in 1 2; do
   for lib in "$@"; do
-    FLOCK_LIB=$PWD/marl_range_flocking_amd/_build/$lib timeout -k 10 200 python bench.py --steps 100 > gpurun_out/ab_$lib.json 2>/dev/null
-    python -c "import json;d=json.load(open('gpurun_out/ab_$lib.json'));print('$lib', round(d['roofline']['kernel_ms']*1000,2), 'us kernel', round(d['ms_per_step']*1000,1), 'us/step')"
+    FLOCK_LIB=$PWD/marl_range_flocking_amd/_build/$lib timeout -k 10 200 python bench.py --full --steps 100 > ${OUT_ROOT:-out}/ab_$lib.json 2>/dev/null
+    python -c "import json;d=json.load(open('${OUT_ROOT:-out}/ab_$lib.json'));print('$lib', round(d['roofline']['kernel_ms']*1000,2), 'us kernel', round(d['ms_per_step']*1000,1), 'us/step')"
   done
 done

@@ -7,7 +7,7 @@ NP=${NPROC:-2}
 OUT=gpurun_out/rehearsal$NP; mkdir -p $OUT
 export FLOCK_DIST_BACKEND=gloo
 run() { local name=$1; shift; timeout -k 10 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node $NP \
-  --master-addr 127.0.0.1 --master-port $((29500 + RANDOM % 1000)) bench.py --gpus $NP --no-cpu-baseline "$@" \
+  --master-addr 127.0.0.1 --master-port $((29500 + RANDOM % 1000)) bench.py --gpus $NP --full --no-cpu-baseline "$@" \
   > $OUT/$name.json 2> $OUT/$name.err; local rc=$?; echo "rc($name)=$rc"; tail -c 700 $OUT/$name.json; echo;
   [ $rc -eq 0 ] || { tail -20 $OUT/$name.err; exit $rc; }; }
 for c in ${CONFIGS:-3 5 4}; do

@@ -15,10 +15,10 @@ if [ "$TESTS" != "none" ]; then
   tail -2 $OUT/pytest.txt
 fi
 if [ "$BENCH" != "none" ]; then
-  step bench.json 300 python bench.py $BENCH --no-cpu-baseline
+  step bench.json 300 python bench.py --full $BENCH --no-cpu-baseline
   tail -c 900 $OUT/bench.json; echo
   if [ "${TRACE:-0}" = "1" ]; then
-    step trace.log 300 rocprofv3 --kernel-trace --stats -d $OUT/trace -o run --output-format csv -- python3 bench.py $BENCH --no-cpu-baseline
+    step trace.log 300 rocprofv3 --kernel-trace --stats -d $OUT/trace -o run --output-format csv -- python3 bench.py --full $BENCH --no-cpu-baseline
   fi
 fi
 echo ALLDONE

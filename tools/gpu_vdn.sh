@@ -5,6 +5,6 @@ step pytest.txt 300 python -u -m pytest tests/test_gpu_learn_kernels.py tests/te
 tail -2 $OUT/pytest.txt
 step vdn_profile.txt 300 python tools/vdn_profile.py
 head -3 $OUT/vdn_profile.txt
-step bench_config4.json 300 python bench.py --config 4 --no-cpu-baseline
+step bench_config4.json 300 python bench.py --full --config 4 --no-cpu-baseline
 head -c 400 $OUT/bench_config4.json
 echo ALLDONE
