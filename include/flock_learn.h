@@ -11,6 +11,8 @@
  *   flock_grad_norm    torch.nn.utils.clip_grad_norm_ (vdn/train_flock.py:42): out[0] = ||g||_2,
  *                      out[1] = min(max_norm / (||g|| + 1e-6), 1); pass out+1 as flock_adam_step's grad_scale
  *   flock_gru_fwd/bwd  nn.GRUCell elementwise part (maddpg_official_rnn/net.py:33,118, vdn/net.py:24)
+ *   flock_vdn_act      QNet.sample_action of every agent on every env row (vdn/net.py:27-37, :52-58;
+ *                      vdn/train_flock.py:93), one launch
  *   flock_gather_rows  replay minibatch / chunk gather (maddpg_official_rnn/memory_rnn.py:69-99,
  *                      vdn/utils.py:31-60, maddpg_shared_critic/utils.py:65-76)
  *   flock_scatter_rows replay insertion (memory_rnn.py:53-67, maddpg_shared_critic/utils.py:47-54)
@@ -92,6 +94,28 @@ int flock_vdn_feat_fwd(void* stream, int A, int R, int B, int n_in, const float*
 int flock_vdn_feat_bwd(void* stream, int A, int R, int B, int n_in, const float* x, int64_t x_sa, int64_t x_sc,
                        int64_t x_sb, const float* w2, const float* w_ih, const float* y1, const float* y2,
                        const float* dgi, float* dw1, float* db1, float* dw2, float* db2, float* dw_ih, float* db_ih);
+
+/* The acting step of the VDN QNet for every env row b < B and agent a < A in one launch (learners/vdn/net.py:27-37
+ * forward and :52-58 sample_action; replaces the per-agent layers, the GRUCell, the q head, argmax and where):
+ *   y1 = relu(w1 x + b1), y2 = relu(w2 y1 + b2), h' = GRUCell(y2, h) (flock_gru_fwd's gate math), q = w_q h' + b_q,
+ *   action = coin[b] <= epsilon ? rnd[b][a] : argmax_j q[j] (the lowest j among equal maxima).
+ * Parameters stacked over agents, contiguous: w1 [A][64][n_obs], b1 [A][64], w2 [A][32][64], b2 [A][32],
+ * w_ih / w_hh [A][96][32], b_ih / b_hh [A][96], w_q [A][n_actions][32], b_q [A][n_actions].
+ * Element (b, a, f) of obs / h_in / h_out at base + b*_sb + a*_sa + f (strides in elements, last dimension
+ * contiguous: [B][A][.] and agent-major [A][B][.] alike); hidden rows are 32 floats, 16-byte aligned; h_out must not
+ * overlap h_in. action: the id of (b, a) at action[b*action_sb + a*action_sa], f32 (action_int64 = 0) or int64.
+ * q_out (may be NULL): q of (b, a) at q_out + b*q_sb + a*q_sa, n_actions floats. coin [B] f32 and rnd [B][A] int64
+ * (ids in [0, n_actions)) go together; both NULL: every row is greedy. reset [B] u8 (may be NULL): rows where it is
+ * nonzero read h = 0 in place of h_in (an episode start). row_split: blocks per agent (0: chosen to fill the device).
+ * Limits: 1 <= n_obs <= 16, 1 <= n_actions <= 16 (-2); NULL required pointer -3; overlap, misaligned hidden rows or a
+ * negative row_split -5; B == 0 or A == 0: 0 without a launch. */
+int flock_vdn_act(void* stream, int A, int B, int n_obs, int n_actions, const float* w1, const float* b1,
+                  const float* w2, const float* b2, const float* w_ih, const float* w_hh, const float* b_ih,
+                  const float* b_hh, const float* w_q, const float* b_q, const float* obs, int64_t obs_sb,
+                  int64_t obs_sa, const float* h_in, int64_t h_in_sb, int64_t h_in_sa, float* h_out, int64_t h_out_sb,
+                  int64_t h_out_sa, void* action, int64_t action_sb, int64_t action_sa, float* q_out, int64_t q_sb,
+                  int64_t q_sa, const float* coin, const int64_t* rnd, const uint8_t* reset, float epsilon,
+                  int action_int64, int row_split);
 
 /* gather: dst[r][:] = src[idx[r]][:]; scatter: dst[idx[r]][:] = src[r][:]; rows of `width` floats. */
 int flock_gather_rows(void* stream, int64_t rows, int64_t width, const float* src, const int64_t* idx, float* dst);

@@ -16,6 +16,8 @@
 
 #pragma clang fp contract(off)
 
+#include "learn_device.h"
+
 namespace flock_learn_internal {
 thread_local char g_err[256] = "";
 int fail(int code, const char* msg) {
@@ -31,6 +33,7 @@ int launched() {
 namespace {
 using flock_learn_internal::fail;
 using flock_learn_internal::launched;
+using namespace flock_learn_device;  // sigmoidf_, the feature chain's widths / strides, lds_barrier, mfma_rows
 
 constexpr int kBlock = 256;
 
@@ -213,8 +216,6 @@ __global__ __launch_bounds__(kBlock) void sq_final_kernel(int nparts, const doub
     }
 }
 
-__device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
-
 // nn.GRUCell elementwise part (ATen gru_cell, RNN.cpp): rows of gi = x W_ih^T + b_ih and gh = h W_hh^T + b_hh
 // (gate order r, z, n), h' = (h - n) * z + n. ws keeps (r, z, n, gh_n) for the backward.
 __global__ __launch_bounds__(kBlock) void gru_fwd_kernel(int64_t rows, int H, const float* __restrict__ gi,
@@ -286,28 +287,7 @@ __global__ __launch_bounds__(kBlock) void gru_bwd_kernel(int64_t rows, int H, co
 // Config 4 (512 agents x 320 rows), per launch: lane-per-row FMA with broadcast weight reads 77 us, MFMA tiles over
 // 64-row blocks 72 us (each block's serial load -> compute chain at two blocks per CU), this per-agent walk with
 // the next rows' x in flight 41 us.
-constexpr int kF1 = 64, kF2 = 32, kFG = 96, kFRows = 64, kFMaxIn = 16;
-constexpr int kSW1 = kFMaxIn + 2, kSY1 = kF1 + 2, kSY2 = kF2 + 2;  // LDS row strides (floats)
-using f32x4_t = float __attribute__((ext_vector_type(4)));
-
-// Workgroup barrier for LDS hand-offs only: waits for this wave's LDS operations (lgkmcnt), not for its global loads
-// (__syncthreads() waits for vmcnt(0) too, which would drain the next rows' prefetch at every barrier). The global
-// loads' own waits stay where their registers are first used.
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-// NT column tiles of 16: acc[t] += A[16 rows][K] * W[16 t .. 16 t + 16][K]^T, k in steps of 4 (one MFMA each)
-template <int NT>
-__device__ __forceinline__ void mfma_rows(f32x4_t (&acc)[NT], const float* a, int sa, const float* w, int sw,
-                                          int K, int lane) {
-    const int i = lane & 15, kk = lane >> 4;
-    for (int k = 0; k < K; k += 4) {
-        const float av = a[i * sa + k + kk];
-#pragma unroll
-        for (int t = 0; t < NT; ++t)
-            acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, w[(16 * t + i) * sw + k + kk], acc[t], 0, 0, 0);
-    }
-}
-
+// (layer widths, LDS strides, lds_barrier and mfma_rows: learn_device.h)
 __global__ __launch_bounds__(kBlock) void vdn_feat_fwd_kernel(int R, int B, int NI, const float* __restrict__ x,
                                                               int64_t xa, int64_t xc, int64_t xb,
                                                               const float* __restrict__ W1, const float* __restrict__ b1,

@@ -14,6 +14,7 @@
 //   flock::gru_seq_fwd/_bwd  a whole chunk of GRUCell steps (vdn/train_flock.py:23-36, MADDPG.py:95-132)
 //   flock::gru_seq_q_fwd/_bwd  the same with VDN's q head fused (learners/vdn/net.py:34-37)
 //   flock::vdn_feat_fwd/_bwd the VDN QNet feature chain + GRU input side (vdn/net.py:19-33) and its backward
+//   flock::vdn_act          the VDN QNet's acting step, every (env row, agent) in one launch (vdn/net.py:27-37, :52-58)
 //   flock::gather_rows / scatter_rows / ring_store   replay gather / insert (memory_rnn.py:53-99, vdn/utils.py:18-60,
 //                            maddpg_shared_critic/utils.py:47-76)
 //   flock::sc_prep_snapshot  shared-critic learn() prologue: Philox row sample + minibatch copy (utils.py:65-76)
@@ -447,6 +448,91 @@ void vdn_feat_bwd_meta(const Tensor& x, const Tensor& w2, const Tensor& wi, cons
     vdn_feat_bwd_checks(x, w2, wi, y1, y2, dgi, dw1, db1, dw2, db2, dwi, dbi);
 }
 
+// ----------------------------------------------------------------------------------------------------- vdn_act
+// The acting step of every (env row, agent) in one launch (flock_vdn_act). obs [B, A, n], h_in / h_out [B, A, 32],
+// action [B, A] (f32 or int64 ids), q_out [B, A, n_actions]: the two leading dimensions may have any strides (the
+// agent-major [A, B, .] buffers are passed as their transposed views, a slice of a wider observation tensor is read in
+// place), the last one is contiguous. The parameters are the stacked FlatParams views, contiguous. coin [B] f32 with
+// rnd [B, A] int64 (both or neither), reset [B] bool / u8.
+void rows_of(const Tensor& t, const char* name, at::ScalarType dtype, at::IntArrayRef shape, const Tensor& like) {
+    TORCH_CHECK(t.device() == like.device(), name, " must be on ", like.device(), ", got ", t.device());
+    TORCH_CHECK(t.scalar_type() == dtype, name, " must be ", dtype, ", got ", t.scalar_type());
+    TORCH_CHECK(t.sizes() == shape, name, " must have shape ", shape, ", got ", t.sizes());
+    TORCH_CHECK(t.dim() < 3 || t.size(2) == 1 || t.stride(2) == 1, name,
+                " must have a unit stride in its last dimension");
+}
+void vdn_act_checks(const Tensor& obs, const Tensor& h_in, const Tensor& w1, const Tensor& b1, const Tensor& w2,
+                    const Tensor& b2, const Tensor& wi, const Tensor& wh, const Tensor& bi, const Tensor& bh,
+                    const Tensor& wq, const Tensor& bq, const Tensor& h_out, const Tensor& action,
+                    const optional<Tensor>& q_out, const optional<Tensor>& coin, const optional<Tensor>& rnd,
+                    const optional<Tensor>& reset, int64_t row_split) {
+    TORCH_CHECK(coin.has_value() == rnd.has_value(), "vdn_act: coin and rnd go together (both or neither)");
+    TORCH_CHECK(row_split >= 0, "vdn_act: row_split must be >= 0");
+    if (any_sym(obs, h_in, w1, b1, w2, b2, wi, wh, bi, bh, wq, bq, h_out, action, q_out, coin, rnd, reset)) return;
+    TORCH_CHECK(obs.dim() == 3, "vdn_act: obs must be [B, A, n_obs], got ", obs.sizes());
+    TORCH_CHECK(h_in.dim() == 3, "vdn_act: h_in must be [B, A, 32], got ", h_in.sizes());
+    TORCH_CHECK(wq.dim() == 3, "vdn_act: w_q must be [A, n_actions, 32], got ", wq.sizes());
+    const int64_t B = obs.size(0), A = obs.size(1), n = obs.size(2), na = wq.size(1);
+    TORCH_CHECK(n >= 1 && n <= 16, "vdn_act: n_obs must be in [1, 16], got ", n);
+    TORCH_CHECK(na >= 1 && na <= 16, "vdn_act: n_actions must be in [1, 16], got ", na);
+    TORCH_CHECK(h_in.size(2) == 32, "vdn_act: the hidden width must be 32, got ", h_in.size(2));
+    rows_of(obs, "obs", at::kFloat, {B, A, n}, obs);
+    rows_of(h_in, "h_in", at::kFloat, {B, A, 32}, obs);
+    rows_of(h_out, "h_out", at::kFloat, {B, A, 32}, obs);
+    TORCH_CHECK(action.scalar_type() == at::kFloat || action.scalar_type() == at::kLong,
+                "action must be float32 or int64, got ", action.scalar_type());
+    rows_of(action, "action", action.scalar_type(), {B, A}, obs);
+    if (q_out) rows_of(*q_out, "q_out", at::kFloat, {B, A, na}, obs);
+    shaped(w1, "w1", at::kFloat, {A, 64, n}, obs);
+    shaped(b1, "b1", at::kFloat, {A, 64}, obs);
+    shaped(w2, "w2", at::kFloat, {A, 32, 64}, obs);
+    shaped(b2, "b2", at::kFloat, {A, 32}, obs);
+    shaped(wi, "w_ih", at::kFloat, {A, 96, 32}, obs);
+    shaped(wh, "w_hh", at::kFloat, {A, 96, 32}, obs);
+    shaped(bi, "b_ih", at::kFloat, {A, 96}, obs);
+    shaped(bh, "b_hh", at::kFloat, {A, 96}, obs);
+    shaped(wq, "w_q", at::kFloat, {A, na, 32}, obs);
+    shaped(bq, "b_q", at::kFloat, {A, na}, obs);
+    if (coin) {
+        shaped(*coin, "coin", at::kFloat, {B}, obs);
+        shaped(*rnd, "rnd", at::kLong, {B, A}, obs);
+    }
+    if (reset) {
+        TORCH_CHECK(reset->scalar_type() == at::kBool || reset->scalar_type() == at::kByte,
+                    "reset must be bool or uint8, got ", reset->scalar_type());
+        shaped(*reset, "reset", reset->scalar_type(), {B}, obs);
+    }
+}
+void vdn_act_hip(const Tensor& obs, const Tensor& h_in, const Tensor& w1, const Tensor& b1, const Tensor& w2,
+                 const Tensor& b2, const Tensor& wi, const Tensor& wh, const Tensor& bi, const Tensor& bh,
+                 const Tensor& wq, const Tensor& bq, const Tensor& h_out, const Tensor& action,
+                 const optional<Tensor>& q_out, const optional<Tensor>& coin, const optional<Tensor>& rnd,
+                 const optional<Tensor>& reset, double epsilon, int64_t row_split) {
+    hip_only(obs, "vdn_act");
+    vdn_act_checks(obs, h_in, w1, b1, w2, b2, wi, wh, bi, bh, wq, bq, h_out, action, q_out, coin, rnd, reset,
+                   row_split);
+    TORCH_CHECK(row_split <= INT32_MAX, "vdn_act: row_split too large");
+    const at::OptionalDeviceGuard g(obs.device());
+    rc_check(flock_vdn_act(stream_of(obs), (int)obs.size(1), (int)obs.size(0), (int)obs.size(2), (int)wq.size(1),
+                           ptr<const float>(w1), ptr<const float>(b1), ptr<const float>(w2), ptr<const float>(b2),
+                           ptr<const float>(wi), ptr<const float>(wh), ptr<const float>(bi), ptr<const float>(bh),
+                           ptr<const float>(wq), ptr<const float>(bq), ptr<const float>(obs), obs.stride(0),
+                           obs.stride(1), ptr<const float>(h_in), h_in.stride(0), h_in.stride(1), ptr<float>(h_out),
+                           h_out.stride(0), h_out.stride(1), action.data_ptr(), action.stride(0), action.stride(1),
+                           ptr<float>(q_out), q_out ? q_out->stride(0) : 0, q_out ? q_out->stride(1) : 0,
+                           ptr<const float>(coin), ptr<const int64_t>(rnd), ptr<const uint8_t>(reset), (float)epsilon,
+                           action.scalar_type() == at::kLong ? 1 : 0, (int)row_split),
+             "flock_vdn_act");
+}
+void vdn_act_meta(const Tensor& obs, const Tensor& h_in, const Tensor& w1, const Tensor& b1, const Tensor& w2,
+                  const Tensor& b2, const Tensor& wi, const Tensor& wh, const Tensor& bi, const Tensor& bh,
+                  const Tensor& wq, const Tensor& bq, const Tensor& h_out, const Tensor& action,
+                  const optional<Tensor>& q_out, const optional<Tensor>& coin, const optional<Tensor>& rnd,
+                  const optional<Tensor>& reset, double, int64_t row_split) {
+    vdn_act_checks(obs, h_in, w1, b1, w2, b2, wi, wh, bi, bh, wq, bq, h_out, action, q_out, coin, rnd, reset,
+                   row_split);
+}
+
 // --------------------------------------------------------------------------------- gather_rows / scatter_rows
 // src / dst: [rows_src, ...] f32 rows of `width` floats; idx: int64 of any shape; gather: dst [idx.numel(), width],
 // scatter: src [idx.numel(), width]
@@ -795,6 +881,10 @@ TORCH_LIBRARY_FRAGMENT(flock, m) {
     m.def(
         "vdn_feat_bwd(Tensor x, Tensor w2, Tensor w_ih, Tensor y1, Tensor y2, Tensor dgi, Tensor(a!) dw1, "
         "Tensor(b!) db1, Tensor(c!) dw2, Tensor(d!) db2, Tensor(e!) dw_ih, Tensor(f!) db_ih) -> ()");
+    m.def(
+        "vdn_act(Tensor obs, Tensor h_in, Tensor w1, Tensor b1, Tensor w2, Tensor b2, Tensor w_ih, Tensor w_hh, "
+        "Tensor b_ih, Tensor b_hh, Tensor w_q, Tensor b_q, Tensor(a!) h_out, Tensor(b!) action, Tensor(c!)? q_out, "
+        "Tensor? coin, Tensor? rnd, Tensor? reset, float epsilon=0.0, int row_split=0) -> ()");
     m.def("gather_rows(Tensor src, Tensor idx, Tensor(a!) dst) -> ()");
     m.def("scatter_rows(Tensor src, Tensor idx, Tensor(a!) dst) -> ()");
     m.def("ring_store(Tensor[] src, Tensor(a!)[] dst, int[] kind, int start) -> ()");
@@ -835,6 +925,7 @@ TORCH_LIBRARY_IMPL(flock, CUDA, m) {
     m.impl("gru_seq_q_bwd", &gru_seq_q_bwd_hip);
     m.impl("vdn_feat_fwd", &vdn_feat_fwd_hip);
     m.impl("vdn_feat_bwd", &vdn_feat_bwd_hip);
+    m.impl("vdn_act", &vdn_act_hip);
     m.impl("gather_rows", &gather_rows_hip);
     m.impl("scatter_rows", &scatter_rows_hip);
     m.impl("ring_store", &ring_store_hip);
@@ -857,6 +948,7 @@ TORCH_LIBRARY_IMPL(flock, Meta, m) {
     m.impl("gru_seq_q_bwd", &gru_seq_q_bwd_meta);
     m.impl("vdn_feat_fwd", &vdn_feat_fwd_meta);
     m.impl("vdn_feat_bwd", &vdn_feat_bwd_meta);
+    m.impl("vdn_act", &vdn_act_meta);
     m.impl("gather_rows", &gather_rows_meta);
     m.impl("scatter_rows", &scatter_rows_meta);
     m.impl("ring_store", &ring_store_meta);

@@ -520,6 +520,21 @@ def vdn_feat(x, W1, b1, W2, b2, Wi, bi, fused_bwd=True, grads=None):
     return _VdnFeatFn.apply(x, W1, b1, W2, b2, Wi, bi, save, fused_bwd, grads)
 
 
+def vdn_act(obs, h_in, params, h_out, action, q_out=None, coin=None, rnd=None, reset=None, epsilon=0.0, row_split=0):
+    """The VDN QNet's acting step for every (env row, agent) in one launch (flock::vdn_act, csrc/flock_vdn_act.hip;
+    learners/vdn/net.py:27-37 and :52-58): obs [B,A,n_obs], h_in [B,A,32] -> h_out [B,A,32] (must not overlap h_in),
+    action [B,A] (f32 or int64 ids: coin[b] <= epsilon ? rnd[b,a] : argmax q), q_out [B,A,n_actions] when given.
+    params: the ten stacked [A, ...] tensors in qnet_shapes order (feat1.weight, feat1.bias, feat2.weight, feat2.bias,
+    gru.weight_ih, gru.weight_hh, gru.bias_ih, gru.bias_hh, q.weight, q.bias). The leading two dimensions of obs, the
+    hidden buffers, action and q_out may have any strides. coin [B] f32 and rnd [B,A] int64 together or neither
+    (greedy); reset [B] bool / u8: those rows read a zero hidden state. row_split: blocks per agent (0: automatic)."""
+    params = tuple(params)
+    if len(params) != 10:
+        raise ValueError("vdn_act: ten stacked parameter tensors in qnet_shapes order")
+    _require_cuda(obs)
+    _ops().vdn_act(obs, h_in, *params, h_out, action, q_out, coin, rnd, reset, float(epsilon), int(row_split))
+
+
 def gru_cell_gi(gi, h, W_hh, b_hh):
     """gru_cell from precomputed input-side gate pre-activations gi = x W_ih^T + b_ih [A,B,3H] (a recurrence can
     compute them for every step at once)."""

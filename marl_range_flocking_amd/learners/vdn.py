@@ -19,8 +19,8 @@ import torch
 import torch.nn.functional as F
 
 from .. import dist
-from .core import (gru_seq_q, FlatParams, GradNorm, OverlappedTrain, ReplayRing, blinear, capture_graph, gru_cell,
-                   gru_seq, vdn_feat)
+from .core import (gru_seq_q, FlatParams, GradNorm, OverlappedTrain, ReplayRing, _ops, blinear, capture_graph,
+                   gru_cell, gru_seq, vdn_act, vdn_feat)
 
 HX = 32
 
@@ -123,9 +123,49 @@ class BatchedQNet:
     def init_hidden(self, batch_size=1):
         return torch.zeros((batch_size, self.n_agents, HX), device=self.device)
 
+    def fused_act_ok(self):
+        """The fused acting kernel (flock::vdn_act) serves this network: recurrent, n_obs and n_actions within its
+        limits, hidden width 32, on a HIP device with the custom ops loaded."""
+        if not (self.recurrent and 1 <= self.n_obs <= 16 and 1 <= self.n_actions <= 16 and self.hx_size == 32
+                and self.device.type == "cuda"):
+            return False
+        return hasattr(_ops(), "vdn_act")  # (a library that is not built raises its own error here)
+
     @torch.no_grad()
-    def sample_action(self, obs, hidden, epsilon, generator=None):
-        """net.py:52-58: one exploration coin per batch row; returns float action ids [B, A]."""
+    def act_into(self, obs, h_in, h_out, action, q_out=None, coin=None, rnd=None, epsilon=0.0, reset=None,
+                 row_split=0, P=None):
+        """One flock::vdn_act launch: obs [B,A,n_obs], h_in [B,A,H] -> h_out [B,A,H] (must not overlap h_in), action
+        [B,A] (f32 or int64 ids), q_out [B,A,n_actions] if given. The leading two dimensions may have any strides
+        (agent-major buffers: pass their transposed views). coin [B] / rnd [B,A] int64: rows with coin <= epsilon take
+        rnd (both None: greedy); reset [B] bool: those rows start from a zero hidden state. A missing kernel or a
+        network beyond its limits is an error, never the torch chain."""
+        if not self.fused_act_ok():
+            raise RuntimeError("BatchedQNet: the fused acting kernel needs a recurrent net with n_obs, n_actions <= 16 "
+                               "on a HIP device")
+        self.P.sync_writers()  # an overlapped train() still writing these parameters
+        P = self.P.params if P is None else P
+        if obs.dtype != torch.float32:
+            obs = obs.float()
+        if obs.shape[-1] > 1 and obs.stride(-1) != 1:
+            obs = obs.contiguous()
+        vdn_act(obs, h_in, [P[n] for n in self.P.shapes], h_out, action, q_out=q_out, coin=coin, rnd=rnd,
+                reset=reset, epsilon=epsilon, row_split=row_split)
+
+    @torch.no_grad()
+    def sample_action(self, obs, hidden, epsilon, generator=None, fused=False, reset=None):
+        """net.py:52-58: one exploration coin per batch row; returns float action ids [B, A]. fused: the whole step as
+        one flock::vdn_act launch, on the same draws (the coins, then the random ids, from the same generator) as the
+        torch chain. reset [B] bool: those rows' hidden state is zero (hidden = q.init_hidden() at an episode start)."""
+        if fused:
+            B, A = obs.shape[0], self.n_agents
+            coin = torch.rand((B,), device=self.device, generator=generator)
+            rnd = torch.randint(0, self.n_actions, (B, A), device=self.device, generator=generator)
+            action = torch.empty((B, A), dtype=torch.float32, device=self.device)
+            h_out = torch.empty((B, A, HX), dtype=torch.float32, device=self.device)
+            self.act_into(obs, hidden, h_out, action, coin=coin, rnd=rnd, epsilon=epsilon, reset=reset)
+            return action, h_out
+        if reset is not None:
+            hidden = hidden.masked_fill(reset.bool()[:, None, None], 0.0)
         out, hidden = self(obs, hidden)
         B = out.shape[0]
         mask = torch.rand((B,), device=self.device, generator=generator) <= epsilon
@@ -225,6 +265,49 @@ class VDNLearner:
         (train_flock.py:102): previous obs, action ids as f32, rewards, new obs, the env's any_done."""
         return self.replay.step_slots(n_envs, "s", "a", "r", "s_prime", "done", group=self.A, store_done=True,
                                       action_ids=True, env_done=True)
+
+    @torch.no_grad()
+    def act(self, obs, epsilon, reset=None, greedy=False):
+        """The vectorized loop's sample_action (train_flock.py:88-104): obs [E, A, n_obs] (the env's observation
+        tensor, read in place) -> int64 action ids [E, A], ready for VecFlockEnv.step(..., ring=self.replay_slots(E)).
+        The recurrent state lives here: two device buffers [E, A, 32] (created on first use or when E changes),
+        swapped each call. reset [E] bool (e.g. the env's any_done): those envs start from a zero hidden state
+        (hidden = q.init_hidden() at an episode start), with no host sync. greedy: no draws, argmax everywhere.
+        One flock::vdn_act launch when the network is within its limits (BatchedQNet.fused_act_ok), else the chain."""
+        obs = torch.as_tensor(obs, device=self.device)
+        E, A = obs.shape[0], self.A
+        st = self.__dict__.get("_act_h")
+        if st is None or st[0].shape[0] != E:
+            st = self._act_h = [torch.zeros((E, A, HX), device=self.device) for _ in range(2)]
+        h_in, h_out = st
+        coin = rnd = None
+        if not greedy:  # sample_action's draws, in its order (net.py:54-55)
+            coin = torch.rand((E,), device=self.device, generator=self.gen)
+            rnd = torch.randint(0, self.n_actions, (E, A), device=self.device, generator=self.gen)
+        if self.q.fused_act_ok():
+            action = torch.empty((E, A), dtype=torch.int64, device=self.device)
+            self.q.act_into(obs, h_in, h_out, action, coin=coin, rnd=rnd, epsilon=epsilon, reset=reset)
+        else:
+            if reset is not None:
+                h_in = h_in.masked_fill(reset.bool()[:, None, None], 0.0)
+            out, h = self.q(obs.float(), h_in)
+            action = out.argmax(dim=2)
+            if not greedy:
+                action = torch.where((coin <= epsilon)[:, None], rnd, action)
+            h_out.copy_(h)
+        self._act_h = [h_out, st[0]]
+        return action
+
+    def act_hidden(self):
+        """The hidden state [E, A, 32] the next act() starts from (None before the first call)."""
+        st = self.__dict__.get("_act_h")
+        return None if st is None else st[0]
+
+    def reset_hidden(self):
+        """hidden = q.init_hidden() for every env (train_flock.py:91)."""
+        st = self.__dict__.get("_act_h")
+        if st is not None:
+            st[0].zero_()
 
     def size(self):
         return len(self.replay)
