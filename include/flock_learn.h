@@ -13,6 +13,8 @@
  *   flock_gru_fwd/bwd  nn.GRUCell elementwise part (maddpg_official_rnn/net.py:33,118, vdn/net.py:24)
  *   flock_vdn_act      QNet.sample_action of every agent on every env row (vdn/net.py:27-37, :52-58;
  *                      vdn/train_flock.py:93), one launch
+ *   flock_maddpg_act   the MADDPG actors' get_actions of every agent on every env row (maddpg_official_rnn/net.py:53-72,
+ *                      agent.py:53-64; maddpg_official/net.py actor forward), one launch
  *   flock_gather_rows  replay minibatch / chunk gather (maddpg_official_rnn/memory_rnn.py:69-99,
  *                      vdn/utils.py:31-60, maddpg_shared_critic/utils.py:65-76)
  *   flock_scatter_rows replay insertion (memory_rnn.py:53-67, maddpg_shared_critic/utils.py:47-54)
@@ -116,6 +118,34 @@ int flock_vdn_act(void* stream, int A, int B, int n_obs, int n_actions, const fl
                   int64_t h_out_sa, void* action, int64_t action_sb, int64_t action_sa, float* q_out, int64_t q_sb,
                   int64_t q_sa, const float* coin, const int64_t* rnd, const uint8_t* reset, float epsilon,
                   int action_int64, int row_split);
+
+/* The acting step of the MADDPG actors for every env row b < B and agent a < A in one launch (recurrent != 0:
+ * learners/maddpg_official_rnn/net.py:53-72 and agent.py:53-64; recurrent == 0: learners/maddpg_official/net.py, the
+ * feed-forward actor):
+ *   recurrent:    y = fce x + b, h' = GRUCell(y, h) (flock_gru_fwd's gate math), y1 = relu(fc1 h' + b1),
+ *                 y2 = relu(fc2 y1 + b2), action = ((tanh(head y2 + b) + 1) / 2, tanh(head2 y2 + b) * 1.5)
+ *   feed-forward: y1 = relu(fc1 x + b1), y2 = relu(fc2 y1 + b2), action = tanh(head y2 + b) (head = fc3, 2 rows)
+ *   action += noise[b][a][0..1] when noise is given (one f32 add).
+ * Parameters stacked over agents, contiguous: fce_w [A][32][k], fce_b [A][32], w_ih / w_hh [A][96][32], b_ih / b_hh
+ * [A][96], fc1_w [A][h1][32] (feed-forward [A][h1][k]), fc1_b [A][h1], fc2_w [A][h2][h1] (16-byte aligned), fc2_b
+ * [A][h2]; recurrent heads head_w = linear_speed.weight [A][1][h2], head_b [A][1], head2_w = angular_speed.weight
+ * [A][1][h2], head2_b [A][1]; feed-forward head_w = fc3.weight [A][2][h2], head_b [A][2], head2_* unused. The
+ * feed-forward flavour reads no fce / GRU parameter and no hidden state (all may be NULL).
+ * Element (b, a, f) of obs / h_in / h_out / action / noise at base + b*_sb + a*_sa + f (strides in elements, last
+ * dimension contiguous: [B][A][.] and agent-major [A][B][.] alike); hidden rows are 32 floats, 16-byte aligned; h_out
+ * must not overlap h_in. action and noise rows are 2 floats. noise may be NULL (greedy: nothing is read). reset [B] u8
+ * (may be NULL): rows where it is nonzero read h = 0 in place of h_in (an episode start). row_split: blocks per agent
+ * (0: chosen to fill the device); a row's result does not depend on it.
+ * Limits: 1 <= k <= 16, 8 <= h1 <= 512 with h1 a multiple of 8, 1 <= h2 <= 320 (-2); NULL required pointer -3;
+ * overlap, misaligned hidden rows or fc2_w, or a negative row_split -5; B == 0 or A == 0: 0 without a launch. */
+int flock_maddpg_act(void* stream, int A, int B, int k, int h1, int h2, int recurrent, const float* fce_w,
+                     const float* fce_b, const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh,
+                     const float* fc1_w, const float* fc1_b, const float* fc2_w, const float* fc2_b,
+                     const float* head_w, const float* head_b, const float* head2_w, const float* head2_b,
+                     const float* obs, int64_t obs_sb, int64_t obs_sa, const float* h_in, int64_t h_in_sb,
+                     int64_t h_in_sa, float* h_out, int64_t h_out_sb, int64_t h_out_sa, float* action,
+                     int64_t action_sb, int64_t action_sa, const float* noise, int64_t noise_sb, int64_t noise_sa,
+                     const uint8_t* reset, int row_split);
 
 /* gather: dst[r][:] = src[idx[r]][:]; scatter: dst[idx[r]][:] = src[r][:]; rows of `width` floats. */
 int flock_gather_rows(void* stream, int64_t rows, int64_t width, const float* src, const int64_t* idx, float* dst);

@@ -59,6 +59,8 @@ SIGNATURES = {
                           + [_c_void_p] * 11,
     "flock_vdn_act": [_c_void_p] + [_c_int] * 4 + [_c_void_p] * 10
                      + [_c_void_p, ctypes.c_int64, ctypes.c_int64] * 5 + [_c_void_p] * 3 + [_c_float, _c_int, _c_int],
+    "flock_maddpg_act": [_c_void_p] + [_c_int] * 6 + [_c_void_p] * 14
+                        + [_c_void_p, ctypes.c_int64, ctypes.c_int64] * 5 + [_c_void_p, _c_int],
     "flock_gru_seq_fwd": [_c_void_p, _c_int, _c_int, _c_int, _c_int] + [_c_void_p] * 4 + [ctypes.c_int64] * 3
     + [_c_void_p] * 2,
     "flock_gru_seq_bwd": [_c_void_p, _c_int, _c_int, _c_int, _c_int] + [_c_void_p] * 5 + [ctypes.c_int64] * 3

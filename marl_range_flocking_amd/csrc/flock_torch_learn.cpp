@@ -15,6 +15,8 @@
 //   flock::gru_seq_q_fwd/_bwd  the same with VDN's q head fused (learners/vdn/net.py:34-37)
 //   flock::vdn_feat_fwd/_bwd the VDN QNet feature chain + GRU input side (vdn/net.py:19-33) and its backward
 //   flock::vdn_act          the VDN QNet's acting step, every (env row, agent) in one launch (vdn/net.py:27-37, :52-58)
+//   flock::maddpg_act       the MADDPG actors' acting step, every (env row, agent) in one launch (maddpg_official_rnn/
+//                            net.py:53-72, agent.py:53-64; maddpg_official/net.py)
 //   flock::gather_rows / scatter_rows / ring_store   replay gather / insert (memory_rnn.py:53-99, vdn/utils.py:18-60,
 //                            maddpg_shared_critic/utils.py:47-76)
 //   flock::sc_prep_snapshot  shared-critic learn() prologue: Philox row sample + minibatch copy (utils.py:65-76)
@@ -533,6 +535,92 @@ void vdn_act_meta(const Tensor& obs, const Tensor& h_in, const Tensor& w1, const
                    row_split);
 }
 
+// -------------------------------------------------------------------------------------------------- maddpg_act
+// The MADDPG actors' acting step of every (env row, agent) in one launch (flock_maddpg_act). obs [B, A, k], h_in /
+// h_out [B, A, 32], action / noise [B, A, 2]: the two leading dimensions may have any strides (the [N, E, 32] hidden
+// state of get_actions is passed as its transposed view), the last one is contiguous. params: the stacked FlatParams
+// views in actor_shapes order, contiguous: 14 tensors = the recurrent actor (h_in and h_out required), 6 = the
+// feed-forward one (no hidden state: h_in and h_out must be None). reset [B] bool / u8.
+void maddpg_act_checks(const Tensor& obs, const optional<Tensor>& h_in, at::TensorList P, const optional<Tensor>& h_out,
+                       const Tensor& action, const optional<Tensor>& noise, const optional<Tensor>& reset,
+                       int64_t row_split) {
+    TORCH_CHECK(P.size() == 14 || P.size() == 6, "maddpg_act: 14 (recurrent) or 6 (feed-forward) stacked parameter "
+                "tensors in actor_shapes order, got ", P.size());
+    const bool rec = P.size() == 14;
+    TORCH_CHECK(h_in.has_value() == rec && h_out.has_value() == rec, "maddpg_act: h_in and h_out go with the recurrent "
+                "actor (14 parameters) and with it only");
+    TORCH_CHECK(row_split >= 0, "maddpg_act: row_split must be >= 0");
+    if (any_sym(obs, h_in, P, h_out, action, noise, reset)) return;
+    TORCH_CHECK(obs.dim() == 3, "maddpg_act: obs must be [B, A, k], got ", obs.sizes());
+    const Tensor &fc1 = P[rec ? 6 : 0], &fc2 = P[rec ? 8 : 2];
+    TORCH_CHECK(fc1.dim() == 3 && fc2.dim() == 3, "maddpg_act: fc1.weight and fc2.weight must be [A, out, in]");
+    const int64_t B = obs.size(0), A = obs.size(1), k = obs.size(2), h1 = fc1.size(1), h2 = fc2.size(1);
+    TORCH_CHECK(k >= 1 && k <= 16, "maddpg_act: k must be in [1, 16], got ", k);
+    TORCH_CHECK(h1 >= 8 && h1 <= 512 && h1 % 8 == 0, "maddpg_act: h1 must be a multiple of 8 in [8, 512], got ", h1);
+    TORCH_CHECK(h2 >= 1 && h2 <= 320, "maddpg_act: h2 must be in [1, 320], got ", h2);
+    rows_of(obs, "obs", at::kFloat, {B, A, k}, obs);
+    rows_of(action, "action", at::kFloat, {B, A, 2}, obs);
+    if (noise) rows_of(*noise, "noise", at::kFloat, {B, A, 2}, obs);
+    if (rec) {
+        TORCH_CHECK(h_in->dim() == 3 && h_in->size(2) == 32, "maddpg_act: the hidden state must be [B, A, 32], got ",
+                    h_in->sizes());
+        rows_of(*h_in, "h_in", at::kFloat, {B, A, 32}, obs);
+        rows_of(*h_out, "h_out", at::kFloat, {B, A, 32}, obs);
+        shaped(P[0], "fce.weight", at::kFloat, {A, 32, k}, obs);
+        shaped(P[1], "fce.bias", at::kFloat, {A, 32}, obs);
+        shaped(P[2], "gru.weight_ih", at::kFloat, {A, 96, 32}, obs);
+        shaped(P[3], "gru.weight_hh", at::kFloat, {A, 96, 32}, obs);
+        shaped(P[4], "gru.bias_ih", at::kFloat, {A, 96}, obs);
+        shaped(P[5], "gru.bias_hh", at::kFloat, {A, 96}, obs);
+        shaped(P[6], "fc1.weight", at::kFloat, {A, h1, 32}, obs);
+        shaped(P[7], "fc1.bias", at::kFloat, {A, h1}, obs);
+        shaped(P[8], "fc2.weight", at::kFloat, {A, h2, h1}, obs);
+        shaped(P[9], "fc2.bias", at::kFloat, {A, h2}, obs);
+        shaped(P[10], "linear_speed.weight", at::kFloat, {A, 1, h2}, obs);
+        shaped(P[11], "linear_speed.bias", at::kFloat, {A, 1}, obs);
+        shaped(P[12], "angular_speed.weight", at::kFloat, {A, 1, h2}, obs);
+        shaped(P[13], "angular_speed.bias", at::kFloat, {A, 1}, obs);
+    } else {
+        shaped(P[0], "fc1.weight", at::kFloat, {A, h1, k}, obs);
+        shaped(P[1], "fc1.bias", at::kFloat, {A, h1}, obs);
+        shaped(P[2], "fc2.weight", at::kFloat, {A, h2, h1}, obs);
+        shaped(P[3], "fc2.bias", at::kFloat, {A, h2}, obs);
+        shaped(P[4], "fc3.weight", at::kFloat, {A, 2, h2}, obs);
+        shaped(P[5], "fc3.bias", at::kFloat, {A, 2}, obs);
+    }
+    if (reset) {
+        TORCH_CHECK(reset->scalar_type() == at::kBool || reset->scalar_type() == at::kByte,
+                    "reset must be bool or uint8, got ", reset->scalar_type());
+        shaped(*reset, "reset", reset->scalar_type(), {B}, obs);
+    }
+}
+void maddpg_act_hip(const Tensor& obs, const optional<Tensor>& h_in, at::TensorList P, const optional<Tensor>& h_out,
+                    const Tensor& action, const optional<Tensor>& noise, const optional<Tensor>& reset,
+                    int64_t row_split) {
+    hip_only(obs, "maddpg_act");
+    maddpg_act_checks(obs, h_in, P, h_out, action, noise, reset, row_split);
+    TORCH_CHECK(row_split <= INT32_MAX, "maddpg_act: row_split too large");
+    const bool rec = P.size() == 14;
+    const float* w[14] = {};
+    for (size_t i = 0; i < P.size(); ++i) w[rec ? i : i + 6] = ptr<const float>(P[i]);  // feed-forward: fc1 .. head
+    const at::OptionalDeviceGuard g(obs.device());
+    rc_check(flock_maddpg_act(stream_of(obs), (int)obs.size(1), (int)obs.size(0), (int)obs.size(2),
+                              (int)P[rec ? 6 : 0].size(1), (int)P[rec ? 8 : 2].size(1), rec ? 1 : 0, w[0], w[1], w[2],
+                              w[3], w[4], w[5], w[6], w[7], w[8], w[9], w[10], w[11], w[12], w[13],
+                              ptr<const float>(obs), obs.stride(0), obs.stride(1), ptr<const float>(h_in),
+                              rec ? h_in->stride(0) : 0, rec ? h_in->stride(1) : 0, ptr<float>(h_out),
+                              rec ? h_out->stride(0) : 0, rec ? h_out->stride(1) : 0, ptr<float>(action),
+                              action.stride(0), action.stride(1), ptr<const float>(noise),
+                              noise ? noise->stride(0) : 0, noise ? noise->stride(1) : 0, ptr<const uint8_t>(reset),
+                              (int)row_split),
+             "flock_maddpg_act");
+}
+void maddpg_act_meta(const Tensor& obs, const optional<Tensor>& h_in, at::TensorList P, const optional<Tensor>& h_out,
+                     const Tensor& action, const optional<Tensor>& noise, const optional<Tensor>& reset,
+                     int64_t row_split) {
+    maddpg_act_checks(obs, h_in, P, h_out, action, noise, reset, row_split);
+}
+
 // --------------------------------------------------------------------------------- gather_rows / scatter_rows
 // src / dst: [rows_src, ...] f32 rows of `width` floats; idx: int64 of any shape; gather: dst [idx.numel(), width],
 // scatter: src [idx.numel(), width]
@@ -885,6 +973,9 @@ TORCH_LIBRARY_FRAGMENT(flock, m) {
         "vdn_act(Tensor obs, Tensor h_in, Tensor w1, Tensor b1, Tensor w2, Tensor b2, Tensor w_ih, Tensor w_hh, "
         "Tensor b_ih, Tensor b_hh, Tensor w_q, Tensor b_q, Tensor(a!) h_out, Tensor(b!) action, Tensor(c!)? q_out, "
         "Tensor? coin, Tensor? rnd, Tensor? reset, float epsilon=0.0, int row_split=0) -> ()");
+    m.def(
+        "maddpg_act(Tensor obs, Tensor? h_in, Tensor[] params, Tensor(a!)? h_out, Tensor(b!) action, Tensor? noise, "
+        "Tensor? reset, int row_split=0) -> ()");
     m.def("gather_rows(Tensor src, Tensor idx, Tensor(a!) dst) -> ()");
     m.def("scatter_rows(Tensor src, Tensor idx, Tensor(a!) dst) -> ()");
     m.def("ring_store(Tensor[] src, Tensor(a!)[] dst, int[] kind, int start) -> ()");
@@ -926,6 +1017,7 @@ TORCH_LIBRARY_IMPL(flock, CUDA, m) {
     m.impl("vdn_feat_fwd", &vdn_feat_fwd_hip);
     m.impl("vdn_feat_bwd", &vdn_feat_bwd_hip);
     m.impl("vdn_act", &vdn_act_hip);
+    m.impl("maddpg_act", &maddpg_act_hip);
     m.impl("gather_rows", &gather_rows_hip);
     m.impl("scatter_rows", &scatter_rows_hip);
     m.impl("ring_store", &ring_store_hip);
@@ -949,6 +1041,7 @@ TORCH_LIBRARY_IMPL(flock, Meta, m) {
     m.impl("vdn_feat_fwd", &vdn_feat_fwd_meta);
     m.impl("vdn_feat_bwd", &vdn_feat_bwd_meta);
     m.impl("vdn_act", &vdn_act_meta);
+    m.impl("maddpg_act", &maddpg_act_meta);
     m.impl("gather_rows", &gather_rows_meta);
     m.impl("scatter_rows", &scatter_rows_meta);
     m.impl("ring_store", &ring_store_meta);

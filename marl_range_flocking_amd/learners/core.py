@@ -535,6 +535,22 @@ def vdn_act(obs, h_in, params, h_out, action, q_out=None, coin=None, rnd=None, r
     _ops().vdn_act(obs, h_in, *params, h_out, action, q_out, coin, rnd, reset, float(epsilon), int(row_split))
 
 
+def maddpg_act(obs, h_in, params, h_out, action, noise=None, reset=None, row_split=0):
+    """The MADDPG actors' acting step for every (env row, agent) in one launch (flock::maddpg_act,
+    csrc/flock_maddpg_act.hip; learners/maddpg_official_rnn/net.py:53-72 and agent.py:53-64, or the feed-forward
+    learners/maddpg_official/net.py): obs [B,A,k], h_in [B,A,32] -> h_out [B,A,32] (must not overlap h_in), action
+    [B,A,2] (+ noise [B,A,2] when given, one f32 add). params: the stacked [A, ...] tensors in actor_shapes order, 14
+    for the recurrent actor, 6 for the feed-forward one (then h_in and h_out are None). The leading two dimensions of
+    obs, the hidden buffers, action and noise may have any strides. reset [B] bool / u8: those rows read a zero hidden
+    state. row_split: blocks per agent (0: automatic)."""
+    params = list(params)
+    if len(params) not in (14, 6):
+        raise ValueError("maddpg_act: 14 (recurrent) or 6 (feed-forward) stacked parameter tensors in actor_shapes "
+                         "order")
+    _require_cuda(obs)
+    _ops().maddpg_act(obs, h_in, params, h_out, action, noise, reset, int(row_split))
+
+
 def gru_cell_gi(gi, h, W_hh, b_hh):
     """gru_cell from precomputed input-side gate pre-activations gi = x W_ih^T + b_ih [A,B,3H] (a recurrence can
     compute them for every step at once)."""

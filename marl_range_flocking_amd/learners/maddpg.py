@@ -34,7 +34,7 @@ import torch.nn.functional as F
 
 from .. import dist
 from .core import (FlatParams, OverlappedTrain, ReplayRing, _ops, blinear, capture_graph, gru_cell, gru_seq, linear_t,
-                   shared_linear)
+                   maddpg_act, shared_linear)
 
 HR = 32  # hidden_rnn (net.py:15,100)
 
@@ -243,6 +243,7 @@ class MADDPGLearner:
         self._shared_obs_bad = None  # device flag: a shared_obs record whose actor / critic observations differed
         self.gen = torch.Generator(device=self.device).manual_seed(seed)
         self.N, self.k, self.recurrent, self.h1 = n_agents, k, recurrent, hidden1
+        self.h2, self.n_actions = hidden2, n_actions
         self.actor_lr, self.critic_lr, self.gamma, self.tau = actor_lr, critic_lr, gamma, tau
         self.B, self.C = batch_size, (chunk_size if recurrent else 1)
         self.min_size_buffer = min_size_buffer
@@ -297,22 +298,114 @@ class MADDPGLearner:
     def init_hidden(self, envs=1):
         return torch.zeros((self.N, envs, HR), device=self.device)
 
+    def fused_act_ok(self):
+        """The fused acting kernel (flock::maddpg_act) serves these actors: k, hidden1 and hidden2 within its limits,
+        two actions, on a HIP device with the custom ops loaded."""
+        if not (1 <= self.k <= 16 and 8 <= self.h1 <= 512 and self.h1 % 8 == 0 and 1 <= self.h2 <= 320
+                and self.n_actions == 2 and self.device.type == "cuda"):
+            return False
+        return hasattr(_ops(), "maddpg_act")  # (a library that is not built raises its own error here)
+
     @torch.no_grad()
-    def get_actions(self, actor_states, hidden=None, test=False):
+    def act_into(self, obs, h_in, h_out, action, noise=None, reset=None, row_split=0):
+        """One flock::maddpg_act launch: obs [B,N,k], h_in [B,N,32] -> h_out [B,N,32] (must not overlap h_in; both None
+        for the feed-forward actors), action [B,N,2] (+ noise [B,N,2] when given). The leading two dimensions may have
+        any strides (agent-major buffers: pass their transposed views). reset [B] bool: those rows start from a zero
+        hidden state. A missing kernel or a network beyond its limits is an error, never the torch chain."""
+        if not self.fused_act_ok():
+            raise RuntimeError("MADDPGLearner: the fused acting kernel needs k <= 16, hidden1 a multiple of 8 in "
+                               "[8, 512], hidden2 <= 320 and two actions, on a HIP device")
+        self.sync()  # an overlapped train() still writing the networks
+        if obs.dtype != torch.float32:
+            obs = obs.float()
+        if obs.shape[-1] > 1 and obs.stride(-1) != 1:
+            obs = obs.contiguous()
+        maddpg_act(obs, h_in, [self.actors.view(self.actors.data, n) for n in self.actors.shapes], h_out, action,
+                   noise=noise, reset=reset, row_split=row_split)
+
+    @torch.no_grad()
+    def get_actions(self, actor_states, hidden=None, test=False, fused=False, reset=None):
         """actor_states [N, k] (one env) or [E, N, k]; hidden [N, E, 32] -> (actions like actor_states[..., :2],
-        hidden'). Noise: the shared OU process, sampled agent after agent (agent.py:53-64)."""
+        hidden'). Noise: the shared OU process, sampled agent after agent (agent.py:53-64). fused: the whole step as one
+        flock::maddpg_act launch, on the same OU draw as the torch chain; hidden and hidden' keep the [N, E, 32] layout
+        (read and written through strided views). reset [E] bool: those envs' hidden state is zero (an episode
+        start)."""
         single = actor_states.dim() == 2
+        if fused:
+            obs = actor_states.reshape(-1, self.N, self.k)  # [E, N, k]
+            E = obs.shape[0]
+            if hidden is None:
+                hidden = self.init_hidden(E)
+            h_out = torch.empty((self.N, E, HR), device=self.device) if self.recurrent else None
+            mu = torch.empty((E, self.N, 2), device=self.device)
+            noise = None if test else self.random_process.sample(self.N, E)
+            self.act_into(obs, hidden.transpose(0, 1) if self.recurrent else None,
+                          h_out.transpose(0, 1) if self.recurrent else None, mu, noise=noise, reset=reset)
+            return (mu[0] if single else mu), (h_out if self.recurrent else hidden)
         self.sync()  # an overlapped train() still writing the networks
         x = actor_states.reshape(-1, self.N, self.k).transpose(0, 1)  # [N, E, k]
         E = x.shape[1]
         if hidden is None:
             hidden = self.init_hidden(E)
+        if reset is not None:
+            hidden = hidden.masked_fill(reset.bool()[None, :, None], 0.0)
         P = {n: self.actors.view(self.actors.data, n) for n in self.actors.shapes}
         mu, h = actor_forward(P, x, hidden, self.recurrent)
         mu = mu.transpose(0, 1)  # [E, N, 2]
         if not test:
             mu = mu + self.random_process.sample(self.N, E)
         return (mu[0] if single else mu), h
+
+    # act() takes the kernel whenever it serves the network (measured faster than the chain: DESIGN.md §3.5)
+    fused_act_default = True
+
+    @torch.no_grad()
+    def act(self, obs, reset=None, test=False):
+        """The vectorized loop's get_actions: obs [E, N, k] (the env's observation tensor, read in place) -> actions
+        [E, N, 2], ready for VecFlockEnv.step(actions, ring=self.replay_slots(E), auto_reset=True). The recurrent state
+        lives here: two device buffers [E, N, 32] (created on first use or when E changes), swapped each call. reset
+        [E] bool (e.g. the env's any_done): those envs start from a zero hidden state, with no host sync. test: no
+        noise (and no draw). One flock::maddpg_act launch when the network is within its limits (fused_act_ok), else
+        the chain."""
+        obs = torch.as_tensor(obs, device=self.device)
+        E, N = obs.shape[0], self.N
+        h_in = h_out = st = None
+        if self.recurrent:
+            st = self.__dict__.get("_act_h")
+            if st is None or st[0].shape[0] != E:
+                st = self._act_h = [torch.zeros((E, N, HR), device=self.device) for _ in range(2)]
+            h_in, h_out = st
+        noise = None if test else self.random_process.sample(N, E)
+        if self.fused_act_default and self.fused_act_ok():
+            action = torch.empty((E, N, 2), device=self.device)
+            self.act_into(obs, h_in, h_out, action, noise=noise, reset=reset)
+        else:
+            self.sync()
+            hc = h_in.transpose(0, 1) if self.recurrent else self.init_hidden(E)
+            if reset is not None:
+                hc = hc.masked_fill(reset.bool()[None, :, None], 0.0)
+            P = {n: self.actors.view(self.actors.data, n) for n in self.actors.shapes}
+            mu, h = actor_forward(P, obs.float().transpose(0, 1), hc, self.recurrent)
+            action = mu.transpose(0, 1)
+            if noise is not None:
+                action = action + noise
+            if self.recurrent:
+                h_out.copy_(h.transpose(0, 1))
+        if self.recurrent:
+            self._act_h = [h_out, st[0]]
+        return action
+
+    def act_hidden(self):
+        """The hidden state [E, N, 32] the next act() starts from (None before the first call, and for the
+        feed-forward actors)."""
+        st = self.__dict__.get("_act_h")
+        return None if st is None else st[0]
+
+    def reset_hidden(self):
+        """A zero hidden state for every env (init_hidden at the start of a run)."""
+        st = self.__dict__.get("_act_h")
+        if st is not None:
+            st[0].zero_()
 
     def reset_random_process(self):
         self.random_process.reset_states()
