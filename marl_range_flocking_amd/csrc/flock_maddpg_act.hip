@@ -11,14 +11,12 @@
 // its hidden state in and out, its two noise values and its two actions.
 //
 // Layout. A block of 4 waves owns ONE agent and walks a run of that agent's 64-row tiles; wave w takes rows [16 w,
-// 16 w + 16) of each tile. Every layer is f32 MFMA (v_mfma_f32_16x16x4_f32) computed TRANSPOSED, out^T = W act^T, as in
-// flock_vdn_act.hip: the A operand is a weight tile (16 output features x 4 k, from LDS), the B operand the
-// activations (4 k x 16 rows, from registers), and lane (j, g) = (lane & 15, lane >> 4) ends with features 16 T + 4 g + v
-// (v = 0..3) of row j for every 16-feature tile T — which is what the next layer's B operand wants from it for
-// k = 16 T + 4 g + v. So fce, both gate products, the GRU cell, fc1, fc2 and the two head dot products pass their
-// activations in registers; LDS holds weights only.
-//   Per tile, recurrent flavour: fce.weight and the two GRU matrices (26.9 KB, vdn_act's swizzle) are staged, the GRU
-// step runs and h' is stored as h was loaded (two 16-B accesses per lane, the four lanes of a row cover its 128 B).
+// 16 w + 16) of each tile. Every layer is f32 MFMA (v_mfma_f32_16x16x4_f32) computed TRANSPOSED, out^T = W act^T, as
+// flock_vdn_act.hip's header tells: the A operand is a weight tile from LDS, the B operand the activations from
+// registers, and what lane (j, g) ends a layer with is what the next layer's B operand wants from it. So fce, both gate
+// products, the GRU cell, fc1, fc2 and the two head dot products keep their activations in registers; LDS has weights.
+//   Per tile, recurrent flavour: fce.weight and the two GRU matrices (26.9 KB) are staged, the GRU step runs and h' is
+// stored as h was loaded: act_device.h's staging, small-input layer, gru_step and hidden-state accesses.
 //   Then fc1 and fc2 run together, chunk by chunk: chunk c holds fc1.weight rows [16 c, 16 c + 16) (16 x 32, the
 // 16 fc1 features that are fc2's k = 16 c .. 16 c + 15) and fc2.weight[:, 16 c .. 16 c + 15] (16 NT rows, pitch 20
 // floats: the 16-B fragment reads of 8 consecutive rows fall on distinct 16-B bank groups). A wave computes its 16
@@ -26,7 +24,7 @@
 // one 16-B LDS read for 4 MFMAs. y1 is never whole anywhere: 4 registers; y2 is the 4 NT accumulators. The chunks are
 // double-buffered: one LDS-only barrier per chunk, the next chunk's global loads in flight (registers) meanwhile.
 //   fc2.weight (480 KB an agent at 400 x 300) does not fit LDS, so every tile streams it from L2 as sc_act16_kernel
-// does; all blocks of an agent run on one XCD (work item w = xcd_first(b % 8) + b / 8) to keep it in that XCD's L2.
+// does; all blocks of an agent run on one XCD (act_device.h's row_run) to keep it in that XCD's L2.
 // Widths that do not fill a tile are zero-padded in LDS (weight rows and columns, biases, head rows): padded fc1
 // features are relu(0) = 0 against zero fc2 columns, padded fc2 features are relu(0) = 0 against zero head weights.
 // A row's result depends on that row and the weights only: not on its place in the tile, the block or the grid.
@@ -36,27 +34,25 @@
 #include <stdint.h>
 #include <stdlib.h>
 
+#include "act_host.h"
 #include "flock_learn.h"
-#include "learn_internal.h"
 
 #pragma clang fp contract(off)
 
-#include "learn_device.h"
+#include "act_device.h"
 
 namespace {
 using flock_learn_internal::fail;
 using flock_learn_internal::launched;
-using namespace flock_learn_device;
+using namespace flock_act_host;
+using namespace flock_act_device;  // kH: the GRU width = fc1's input width
 
-constexpr int kBlock = 256;
-constexpr int kH = 32;                 // GRU width = fc1's input width
 constexpr int kRows = 64;              // rows per tile (16 per wave)
-constexpr int kMaxIn = 16, kMaxH1 = 512, kMaxH2 = 320;
+constexpr int kMaxIn = kFMaxIn, kMaxH1 = 512, kMaxH2 = 320;
 constexpr int kKC = 16;                // fc1 features per chunk = depth of a chunk's fc2.weight slice
 constexpr int kP2 = kKC + 4;           // pitch of a staged fc2.weight row (floats)
 constexpr int kW1C = kKC * kH;         // a chunk's fc1.weight rows
 constexpr int kSF = kMaxIn + 2;        // widest fce.weight row pitch
-constexpr int kG = 3 * kH;             // gate rows
 constexpr int kGruFloats = kH * kSF + 2 * kG * kH;  // fce.weight + weight_ih + weight_hh
 constexpr int kNBias = kH + 2 * kG + 4;             // fce.bias, bias_ih, bias_hh, the two head biases (+ 2 pad)
 
@@ -75,15 +71,6 @@ struct MaddpgActArgs {
     int64_t n_sr, n_sa;
     const uint8_t* reset;
 };
-
-// column swizzle of a 32-wide weight row o (o & 15 = i), as flock_vdn_act.hip
-__device__ __forceinline__ int swz(int i) { return (i & 3) | ((i & 4) << 1) | ((i & 8) << 1); }
-
-template <int NT, int K>
-__device__ __forceinline__ void mfma_wt(f32x4_t (&acc)[NT], const float* wk, float act) {
-#pragma unroll
-    for (int T = 0; T < NT; ++T) acc[T] = __builtin_amdgcn_mfma_f32_16x16x4f32(wk[16 * T * K], act, acc[T], 0, 0, 0);
-}
 
 constexpr int lds_floats(int NT, int H1P) {
     const int chunk = 16 * NT * kP2 + kW1C;
@@ -106,15 +93,9 @@ __global__ __launch_bounds__(kBlock, 2) void maddpg_act_kernel(MaddpgActArgs p) 
     float *sB2 = sB1 + H1P, *sHA = sB2 + NC, *sHB = sHA + NC, *sBs = sHB + NC, *U = sBs + kNBias;
     const float *bsf = sBs, *bsi = sBs + kH, *bsh = bsi + kG, *bsa = bsh + kG;
 
-    // work item of this block: the items of one XCD label (b % 8) are consecutive (flock_vdn_act.hip)
-    const int Wn = p.A * p.S, bx = blockIdx.x, q8 = Wn >> 3, r8 = Wn & 7, xl = bx & 7;
-    const int w = (xl < r8 ? xl * (q8 + 1) : r8 * (q8 + 1) + (xl - r8) * q8) + (bx >> 3);
-    const int64_t a = w / p.S;
-    const int s = w - (int)a * p.S;
-    const int tiles = (p.B + kRows - 1) / kRows, tps = (tiles + p.S - 1) / p.S;
-    const int64_t r_begin = (int64_t)s * tps * kRows;
-    const int64_t r_end = min((int64_t)p.B, r_begin + (int64_t)tps * kRows);
-    if (r_begin >= r_end) return;  // more blocks than row tiles (the whole block leaves)
+    const RowRun run = row_run(p.A, p.S, p.B, kRows);
+    const int64_t a = run.a, r_begin = run.r_begin, r_end = run.r_end;
+    if (r_begin >= r_end) return;
 
     for (int e = tid; e < H1P; e += kBlock) sB1[e] = e < H1 ? p.b1[a * H1 + e] : 0.0f;
     for (int c = tid; c < NC; c += kBlock) {
@@ -138,7 +119,7 @@ __global__ __launch_bounds__(kBlock, 2) void maddpg_act_kernel(MaddpgActArgs p) 
     const int in1 = rec ? kH : K;    // fc1's input width
     const float* W1a = p.W1 + a * H1 * in1;
     const float* W2a = p.W2 + a * H2 * H1;
-    const int K1 = (K + 3) & ~3, sx = K1 + 2;  // fce row pitch 2 (2 u + 1): 16 rows x 2 adjacent k on 32 banks
+    const int K1 = (K + 3) & ~3, sx = K1 + 2;  // fce's row pitch
     float *wf = U, *wi = U + kH * kSF, *wh = wi + kG * kH;
 
     // one chunk's weights on their way from global memory to LDS
@@ -180,74 +161,24 @@ __global__ __launch_bounds__(kBlock, 2) void maddpg_act_kernel(MaddpgActArgs p) 
 #pragma unroll
             for (int s4 = 0; s4 < kMaxIn / 4; ++s4)
                 x[s4] = (ok && 4 * s4 + g < K) ? p.obs[r * p.o_sr + a * p.o_sa + 4 * s4 + g] : 0.0f;
-            {
-                float4 h0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), h1 = h0;
-                if (ok && !(p.reset && p.reset[r])) {  // an episode start reads h = 0
-                    const float* hp = p.hin + r * p.hi_sr + a * p.hi_sa + 4 * g;
-                    h0 = *reinterpret_cast<const float4*>(hp);
-                    h1 = *reinterpret_cast<const float4*>(hp + 16);
-                }
-                h[0][0] = h0.x, h[0][1] = h0.y, h[0][2] = h0.z, h[0][3] = h0.w;
-                h[1][0] = h1.x, h[1][1] = h1.y, h[1][2] = h1.z, h[1][3] = h1.w;
-            }
+            float4 hr[2] = {make_float4(0.0f, 0.0f, 0.0f, 0.0f), make_float4(0.0f, 0.0f, 0.0f, 0.0f)};
+            if (ok && !(p.reset && p.reset[r])) load_h(hr, p.hin + r * p.hi_sr + a * p.hi_sa + 4 * g);  // else h = 0
+            unpack_h(h, hr, false);
             lds_barrier();  // the previous tile's last chunk has been read
-            for (int e = tid; e < kH * K1; e += kBlock) {
-                const int o = e / K1, k = e - o * K1;
-                wf[o * sx + k] = k < K ? p.Wf[(a * kH + o) * K + k] : 0.0f;
-            }
-            for (int e = tid; e < kG * kH; e += kBlock) {
-                const int o = e / kH, k = e % kH, d = o * kH + (k ^ swz(o & 15));
-                wi[d] = p.Wi[a * kG * kH + e];
-                wh[d] = p.Wh[a * kG * kH + e];
-            }
+            stage_small_in(wf, p.Wf, a, kH, K, tid);
+            stage_gates(wi, wh, p.Wi, p.Wh, a, tid);
             lds_barrier();
             float y[2][4];
             {  // fce: 2 feature tiles, k = 4 s + g
                 f32x4_t acc[2] = {};
-                const float* wfl = wf + j * sx + g;
-#pragma unroll
-                for (int s4 = 0; s4 < kMaxIn / 4; ++s4)
-                    if (4 * s4 < K1) {
-#pragma unroll
-                        for (int T = 0; T < 2; ++T)
-                            acc[T] = __builtin_amdgcn_mfma_f32_16x16x4f32(wfl[16 * T * sx + 4 * s4], x[s4], acc[T], 0, 0, 0);
-                    }
+                small_in_layer<2>(acc, wf + j * sx + g, K1, x);
 #pragma unroll
                 for (int T = 0; T < 2; ++T)
 #pragma unroll
                     for (int v = 0; v < 4; ++v) y[T][v] = acc[T][v] + bsf[16 * T + 4 * g + v];
             }
-            {  // both gate products (12 tiles) and the GRU cell on the accumulators, in gru_fwd_kernel's operation order
-                f32x4_t gi[6] = {}, gh[6] = {};
-                const float *wil = wi + j * kH, *whl = wh + j * kH;
-#pragma unroll
-                for (int Tp = 0; Tp < 2; ++Tp)
-#pragma unroll
-                    for (int v = 0; v < 4; ++v) {
-                        const int c = (16 * Tp + v) ^ m;
-                        mfma_wt<6, kH>(gi, wil + c, y[Tp][v]);
-                        mfma_wt<6, kH>(gh, whl + c, h[Tp][v]);
-                    }
-#pragma unroll
-                for (int t = 0; t < 2; ++t)
-#pragma unroll
-                    for (int v = 0; v < 4; ++v) {
-                        const int c = 16 * t + 4 * g + v;
-                        const float air = gi[t][v] + bsi[c], aiz = gi[t + 2][v] + bsi[kH + c],
-                                    ain = gi[t + 4][v] + bsi[2 * kH + c];
-                        const float bhr = gh[t][v] + bsh[c], bhz = gh[t + 2][v] + bsh[kH + c],
-                                    ghn = gh[t + 4][v] + bsh[2 * kH + c];
-                        const float rg = sigmoidf_(bhr + air);
-                        const float zg = sigmoidf_(bhz + aiz);
-                        const float nn = tanhf(ain + ghn * rg);
-                        hv[t][v] = (h[t][v] - nn) * zg + nn;
-                    }
-            }
-            if (ok) {  // h' as h was loaded
-                float* hp = p.hout + r * p.ho_sr + a * p.ho_sa + 4 * g;
-                *reinterpret_cast<float4*>(hp) = make_float4(hv[0][0], hv[0][1], hv[0][2], hv[0][3]);
-                *reinterpret_cast<float4*>(hp + 16) = make_float4(hv[1][0], hv[1][1], hv[1][2], hv[1][3]);
-            }
+            gru_step(hv, y, h, wi + j * kH, wh + j * kH, bsi, bsh, m, g);
+            if (ok) store_h(p.hout + r * p.ho_sr + a * p.ho_sa + 4 * g, hv);  // h' as h was loaded
         } else {
 #pragma unroll
             for (int v = 0; v < 4; ++v) {
@@ -325,14 +256,6 @@ __global__ __launch_bounds__(kBlock, 2) void maddpg_act_kernel(MaddpgActArgs p) 
     }
 }
 
-// [lo, hi) bytes covered by rows b < B, agents a < A of `width` floats at base + b*sr + a*sa
-void extent(const float* base, int A, int B, int64_t sr, int64_t sa, int width, uintptr_t& lo, uintptr_t& hi) {
-    const int64_t dr = (int64_t)(B - 1) * sr, da = (int64_t)(A - 1) * sa;
-    const int64_t mn = (dr < 0 ? dr : 0) + (da < 0 ? da : 0), mx = (dr > 0 ? dr : 0) + (da > 0 ? da : 0);
-    lo = (uintptr_t)(base + mn);
-    hi = (uintptr_t)(base + mx + width);
-}
-
 template <int NT>
 int launch(hipStream_t st, const MaddpgActArgs& p) {
     const size_t lds = sizeof(float) * (size_t)lds_floats(NT, (p.H1 + 15) & ~15);
@@ -358,24 +281,13 @@ extern "C" int flock_maddpg_act(void* stream, int A, int B, int k, int h1, int h
     if (k < 1 || k > kMaxIn) return fail(-2, "flock_maddpg_act: k must be in [1, 16]");
     if (h1 < 8 || h1 > kMaxH1 || (h1 & 7)) return fail(-2, "flock_maddpg_act: h1 must be a multiple of 8 in [8, 512]");
     if (h2 < 1 || h2 > kMaxH2) return fail(-2, "flock_maddpg_act: h2 must be in [1, 320]");
-    const int tiles = (B + kRows - 1) / kRows;
-    if (row_split < 0 || (int64_t)A * (row_split ? row_split : tiles) > INT32_MAX)
-        return fail(-5, "flock_maddpg_act: row_split must be >= 0 and A * row_split fit the grid");
+    // automatic split: about eight work items for each of the 512 resident blocks, so the last to finish are short
+    int S;
+    if (int rc = row_split_of("flock_maddpg_act", A, B, kRows, row_split, 4096, S)) return rc;
     if ((uintptr_t)fc2_w & 15u) return fail(-5, "flock_maddpg_act: fc2.weight must be 16-byte aligned");
-    if (recurrent) {
-        if (((uintptr_t)h_in | (uintptr_t)h_out) & 15u || ((h_in_sb | h_in_sa | h_out_sb | h_out_sa) & 3))
-            return fail(-5, "flock_maddpg_act: hidden rows must be 16-byte aligned");
-        uintptr_t ilo, ihi, olo, ohi;
-        extent(h_in, A, B, h_in_sb, h_in_sa, kH, ilo, ihi);
-        extent(h_out, A, B, h_out_sb, h_out_sa, kH, olo, ohi);
-        if (ilo < ohi && olo < ihi)
-            return fail(-5, "flock_maddpg_act: h_out overlaps h_in (keep two buffers and swap them)");
-    }
-    int S = row_split;
-    if (S == 0) {  // about eight work items for each of the 512 resident blocks: the last ones to finish are short
-        S = (4096 + A - 1) / A;
-        if (S > tiles) S = tiles;
-    }
+    if (recurrent)
+        if (int rc = check_hidden_pair("flock_maddpg_act", A, B, kH, h_in, h_in_sb, h_in_sa, h_out, h_out_sb, h_out_sa))
+            return rc;
     const MaddpgActArgs p{A, B, k, h1, h2, S, recurrent ? 1 : 0, fce_w, fce_b, w_ih, w_hh, b_ih, b_hh, fc1_w, fc1_b,
                           fc2_w, fc2_b, head_w, head_b, head2_w, head2_b, obs, obs_sb, obs_sa, h_in, h_in_sb, h_in_sa,
                           h_out, h_out_sb, h_out_sa, action, action_sb, action_sa, noise, noise_sb, noise_sa, reset};

@@ -463,6 +463,12 @@ void rows_of(const Tensor& t, const char* name, at::ScalarType dtype, at::IntArr
     TORCH_CHECK(t.dim() < 3 || t.size(2) == 1 || t.stride(2) == 1, name,
                 " must have a unit stride in its last dimension");
 }
+void reset_of(const optional<Tensor>& reset, int64_t B, const Tensor& like) {
+    if (!reset) return;
+    TORCH_CHECK(reset->scalar_type() == at::kBool || reset->scalar_type() == at::kByte,
+                "reset must be bool or uint8, got ", reset->scalar_type());
+    shaped(*reset, "reset", reset->scalar_type(), {B}, like);
+}
 void vdn_act_checks(const Tensor& obs, const Tensor& h_in, const Tensor& w1, const Tensor& b1, const Tensor& w2,
                     const Tensor& b2, const Tensor& wi, const Tensor& wh, const Tensor& bi, const Tensor& bh,
                     const Tensor& wq, const Tensor& bq, const Tensor& h_out, const Tensor& action,
@@ -499,11 +505,7 @@ void vdn_act_checks(const Tensor& obs, const Tensor& h_in, const Tensor& w1, con
         shaped(*coin, "coin", at::kFloat, {B}, obs);
         shaped(*rnd, "rnd", at::kLong, {B, A}, obs);
     }
-    if (reset) {
-        TORCH_CHECK(reset->scalar_type() == at::kBool || reset->scalar_type() == at::kByte,
-                    "reset must be bool or uint8, got ", reset->scalar_type());
-        shaped(*reset, "reset", reset->scalar_type(), {B}, obs);
-    }
+    reset_of(reset, B, obs);
 }
 void vdn_act_hip(const Tensor& obs, const Tensor& h_in, const Tensor& w1, const Tensor& b1, const Tensor& w2,
                  const Tensor& b2, const Tensor& wi, const Tensor& wh, const Tensor& bi, const Tensor& bh,
@@ -588,11 +590,7 @@ void maddpg_act_checks(const Tensor& obs, const optional<Tensor>& h_in, at::Tens
         shaped(P[4], "fc3.weight", at::kFloat, {A, 2, h2}, obs);
         shaped(P[5], "fc3.bias", at::kFloat, {A, 2}, obs);
     }
-    if (reset) {
-        TORCH_CHECK(reset->scalar_type() == at::kBool || reset->scalar_type() == at::kByte,
-                    "reset must be bool or uint8, got ", reset->scalar_type());
-        shaped(*reset, "reset", reset->scalar_type(), {B}, obs);
-    }
+    reset_of(reset, B, obs);
 }
 void maddpg_act_hip(const Tensor& obs, const optional<Tensor>& h_in, at::TensorList P, const optional<Tensor>& h_out,
                     const Tensor& action, const optional<Tensor>& noise, const optional<Tensor>& reset,

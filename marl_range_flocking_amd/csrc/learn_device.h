@@ -1,7 +1,7 @@
 // Device helpers shared by the kernels of the VDN QNet: the layer widths of the feature chain, the MFMA accumulator
-// type and the sigmoid of the GRU gates (flock_learn.hip: vdn_feat_fwd/bwd and the GRU kernels; flock_vdn_act.hip: the
-// fused acting step, whose gate math must be gru_fwd_kernel's), and the LDS strides, LDS-only workgroup barrier and f32
-// MFMA row GEMM of the training-side feature kernels. Include after `#pragma clang fp contract(off)`.
+// type and the sigmoid of the GRU gates (flock_learn.hip: vdn_feat_fwd/bwd and the GRU kernels; act_device.h: the GRU
+// step of the fused acting kernels, whose gate math must be gru_fwd_kernel's), and the LDS strides, LDS-only workgroup
+// barrier and f32 MFMA row GEMM of the training-side feature kernels. Include after `#pragma clang fp contract(off)`.
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -551,6 +551,34 @@ def maddpg_act(obs, h_in, params, h_out, action, noise=None, reset=None, row_spl
     _ops().maddpg_act(obs, h_in, params, h_out, action, noise, reset, int(row_split))
 
 
+def act_obs(obs):  # obs as the fused acting ops read it: f32, unit stride in its last dimension (copied only if not)
+    obs = obs.float()
+    return obs.contiguous() if obs.shape[-1] > 1 and obs.stride(-1) != 1 else obs
+
+
+class ActHidden:
+    """The recurrent state of a learner's act(): two device buffers [E, agents, width]. A call reads one and writes the
+    other (the fused kernels refuse an h_out that overlaps h_in); swap() then exchanges their roles."""
+
+    def __init__(self, agents, width, device):
+        self.shape, self.device, self.bufs = (agents, width), device, []
+
+    def pair(self, E):  # (h_in, h_out): zeros on first use and whenever E changes
+        if not self.bufs or self.bufs[0].shape[0] != E:
+            self.bufs = [torch.zeros((E, *self.shape), device=self.device) for _ in range(2)]
+        return tuple(self.bufs)
+
+    def swap(self):
+        self.bufs.reverse()
+
+    def current(self):  # the state the next call starts from; None before the first pair()
+        return self.bufs[0] if self.bufs else None
+
+    def zero(self):  # the next call starts from h = 0
+        if self.bufs:
+            self.bufs[0].zero_()
+
+
 def gru_cell_gi(gi, h, W_hh, b_hh):
     """gru_cell from precomputed input-side gate pre-activations gi = x W_ih^T + b_ih [A,B,3H] (a recurrence can
     compute them for every step at once)."""

@@ -33,8 +33,8 @@ import torch
 import torch.nn.functional as F
 
 from .. import dist
-from .core import (FlatParams, OverlappedTrain, ReplayRing, _ops, blinear, capture_graph, gru_cell, gru_seq, linear_t,
-                   maddpg_act, shared_linear)
+from .core import (ActHidden, FlatParams, OverlappedTrain, ReplayRing, _ops, act_obs, blinear, capture_graph, gru_cell,
+                   gru_seq, linear_t, maddpg_act, shared_linear)
 
 HR = 32  # hidden_rnn (net.py:15,100)
 
@@ -289,6 +289,7 @@ class MADDPGLearner:
         self.losses = torch.zeros(2, device=self.device)
         self.use_graph = use_graph
         self.graph = None
+        self.hidden = ActHidden(n_agents, HR, self.device)
         if self.distributed:
             dist.sync_params(self.actors, group=dist_group)
             if not self.shard:
@@ -316,11 +317,7 @@ class MADDPGLearner:
             raise RuntimeError("MADDPGLearner: the fused acting kernel needs k <= 16, hidden1 a multiple of 8 in "
                                "[8, 512], hidden2 <= 320 and two actions, on a HIP device")
         self.sync()  # an overlapped train() still writing the networks
-        if obs.dtype != torch.float32:
-            obs = obs.float()
-        if obs.shape[-1] > 1 and obs.stride(-1) != 1:
-            obs = obs.contiguous()
-        maddpg_act(obs, h_in, [self.actors.view(self.actors.data, n) for n in self.actors.shapes], h_out, action,
+        maddpg_act(act_obs(obs), h_in, [self.actors.view(self.actors.data, n) for n in self.actors.shapes], h_out, action,
                    noise=noise, reset=reset, row_split=row_split)
 
     @torch.no_grad()
@@ -363,18 +360,12 @@ class MADDPGLearner:
     def act(self, obs, reset=None, test=False):
         """The vectorized loop's get_actions: obs [E, N, k] (the env's observation tensor, read in place) -> actions
         [E, N, 2], ready for VecFlockEnv.step(actions, ring=self.replay_slots(E), auto_reset=True). The recurrent state
-        lives here: two device buffers [E, N, 32] (created on first use or when E changes), swapped each call. reset
-        [E] bool (e.g. the env's any_done): those envs start from a zero hidden state, with no host sync. test: no
-        noise (and no draw). One flock::maddpg_act launch when the network is within its limits (fused_act_ok), else
-        the chain."""
+        [E, N, 32] lives here (self.hidden, an ActHidden). reset [E] bool (e.g. the env's any_done): those envs start
+        from a zero hidden state, with no host sync. test: no noise (and no draw). One flock::maddpg_act launch when the
+        network is within its limits (fused_act_ok), else the chain."""
         obs = torch.as_tensor(obs, device=self.device)
         E, N = obs.shape[0], self.N
-        h_in = h_out = st = None
-        if self.recurrent:
-            st = self.__dict__.get("_act_h")
-            if st is None or st[0].shape[0] != E:
-                st = self._act_h = [torch.zeros((E, N, HR), device=self.device) for _ in range(2)]
-            h_in, h_out = st
+        h_in, h_out = self.hidden.pair(E) if self.recurrent else (None, None)
         noise = None if test else self.random_process.sample(N, E)
         if self.fused_act_default and self.fused_act_ok():
             action = torch.empty((E, N, 2), device=self.device)
@@ -392,20 +383,17 @@ class MADDPGLearner:
             if self.recurrent:
                 h_out.copy_(h.transpose(0, 1))
         if self.recurrent:
-            self._act_h = [h_out, st[0]]
+            self.hidden.swap()
         return action
 
     def act_hidden(self):
         """The hidden state [E, N, 32] the next act() starts from (None before the first call, and for the
         feed-forward actors)."""
-        st = self.__dict__.get("_act_h")
-        return None if st is None else st[0]
+        return self.hidden.current()
 
     def reset_hidden(self):
         """A zero hidden state for every env (init_hidden at the start of a run)."""
-        st = self.__dict__.get("_act_h")
-        if st is not None:
-            st[0].zero_()
+        self.hidden.zero()
 
     def reset_random_process(self):
         self.random_process.reset_states()

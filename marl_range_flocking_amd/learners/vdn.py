@@ -19,8 +19,8 @@ import torch
 import torch.nn.functional as F
 
 from .. import dist
-from .core import (gru_seq_q, FlatParams, GradNorm, OverlappedTrain, ReplayRing, _ops, blinear, capture_graph,
-                   gru_cell, gru_seq, vdn_act, vdn_feat)
+from .core import (gru_seq_q, ActHidden, FlatParams, GradNorm, OverlappedTrain, ReplayRing, _ops, act_obs, blinear,
+                   capture_graph, gru_cell, gru_seq, vdn_act, vdn_feat)
 
 HX = 32
 
@@ -144,11 +144,7 @@ class BatchedQNet:
                                "on a HIP device")
         self.P.sync_writers()  # an overlapped train() still writing these parameters
         P = self.P.params if P is None else P
-        if obs.dtype != torch.float32:
-            obs = obs.float()
-        if obs.shape[-1] > 1 and obs.stride(-1) != 1:
-            obs = obs.contiguous()
-        vdn_act(obs, h_in, [P[n] for n in self.P.shapes], h_out, action, q_out=q_out, coin=coin, rnd=rnd,
+        vdn_act(act_obs(obs), h_in, [P[n] for n in self.P.shapes], h_out, action, q_out=q_out, coin=coin, rnd=rnd,
                 reset=reset, epsilon=epsilon, row_split=row_split)
 
     @torch.no_grad()
@@ -210,6 +206,7 @@ class VDNLearner:
         self.use_graph = use_graph
         self.graph = None
         self.train_leaves = self.q.P.new_leaves()
+        self.hidden = ActHidden(n_agents, HX, self.device)
         self.group = dist_group
         self.distributed = dist.active(dist_group)
         if self.distributed:  # identical replicas: rank 0's initial parameters everywhere
@@ -232,6 +229,7 @@ class VDNLearner:
         self.loss = torch.zeros((), device=self.device)
         self.use_graph, self.graph = use_graph, None
         self.train_leaves = q.P.new_leaves()
+        self.hidden = ActHidden(q.n_agents, HX, self.device)
         self.group, self.distributed = None, False
         return self
 
@@ -270,16 +268,13 @@ class VDNLearner:
     def act(self, obs, epsilon, reset=None, greedy=False):
         """The vectorized loop's sample_action (train_flock.py:88-104): obs [E, A, n_obs] (the env's observation
         tensor, read in place) -> int64 action ids [E, A], ready for VecFlockEnv.step(..., ring=self.replay_slots(E)).
-        The recurrent state lives here: two device buffers [E, A, 32] (created on first use or when E changes),
-        swapped each call. reset [E] bool (e.g. the env's any_done): those envs start from a zero hidden state
-        (hidden = q.init_hidden() at an episode start), with no host sync. greedy: no draws, argmax everywhere.
+        The recurrent state [E, A, 32] lives here (self.hidden, an ActHidden). reset [E] bool (e.g. the env's
+        any_done): those envs start from a zero hidden state (hidden = q.init_hidden() at an episode start), with no
+        host sync. greedy: no draws, argmax everywhere.
         One flock::vdn_act launch when the network is within its limits (BatchedQNet.fused_act_ok), else the chain."""
         obs = torch.as_tensor(obs, device=self.device)
         E, A = obs.shape[0], self.A
-        st = self.__dict__.get("_act_h")
-        if st is None or st[0].shape[0] != E:
-            st = self._act_h = [torch.zeros((E, A, HX), device=self.device) for _ in range(2)]
-        h_in, h_out = st
+        h_in, h_out = self.hidden.pair(E)
         coin = rnd = None
         if not greedy:  # sample_action's draws, in its order (net.py:54-55)
             coin = torch.rand((E,), device=self.device, generator=self.gen)
@@ -295,19 +290,16 @@ class VDNLearner:
             if not greedy:
                 action = torch.where((coin <= epsilon)[:, None], rnd, action)
             h_out.copy_(h)
-        self._act_h = [h_out, st[0]]
+        self.hidden.swap()
         return action
 
     def act_hidden(self):
         """The hidden state [E, A, 32] the next act() starts from (None before the first call)."""
-        st = self.__dict__.get("_act_h")
-        return None if st is None else st[0]
+        return self.hidden.current()
 
     def reset_hidden(self):
         """hidden = q.init_hidden() for every env (train_flock.py:91)."""
-        st = self.__dict__.get("_act_h")
-        if st is not None:
-            st[0].zero_()
+        self.hidden.zero()
 
     def size(self):
         return len(self.replay)

@@ -275,6 +275,34 @@ def test_act_in_the_vectorized_loop(cuda):
     assert L.act_hidden().shape == (3, N, 32)
 
 
+def test_overlap_and_misaligned_hidden_refusal(cuda):
+    """Refused by the C entry before any launch: an h_out that overlaps h_in, and hidden rows that are not 16-byte
+    aligned (a base pointer off by one float; a row pitch of 33 floats)."""
+    from marl_range_flocking_amd.learners.core import _ops
+
+    flock = _ops()
+    A, B, k = 2, 3, 4
+    L = _learner(A, k, 8, 1, cuda)
+    obs, hid = _inputs(B, A, k, cuda)
+    P = [L.actors.view(L.actors.data, n).detach() for n in L.actors.shapes]
+    h, act = torch.zeros(B, A, 32, device=cuda), torch.zeros(B, A, 2, device=cuda)
+    with pytest.raises(RuntimeError, match="overlaps"):
+        flock.maddpg_act(obs, hid, P, hid, act, None, None, 0)
+    both = torch.zeros(B + 1, A, 32, device=cuda)
+    with pytest.raises(RuntimeError, match="overlaps"):
+        flock.maddpg_act(obs, both[:B], P, both[1:], act, None, None, 0)
+    off = torch.zeros(B * A * 32 + 4, device=cuda)[1:1 + B * A * 32].view(B, A, 32)
+    pitch = torch.zeros(B, A, 33, device=cuda)[:, :, :32]
+    for bad in (off, pitch):
+        with pytest.raises(RuntimeError, match="16-byte aligned"):
+            flock.maddpg_act(obs, bad, P, h, act, None, None, 0)
+        with pytest.raises(RuntimeError, match="16-byte aligned"):
+            flock.maddpg_act(obs, hid, P, bad, act, None, None, 0)
+    assert torch.count_nonzero(h).item() == 0 and torch.count_nonzero(act).item() == 0  # nothing was launched
+    flock.maddpg_act(obs, hid, P, h, act, None, None, 0)  # the aligned, disjoint pair is served
+    assert torch.isfinite(h).all() and torch.count_nonzero(h).item() > 0
+
+
 def test_opcheck(cuda):
     from marl_range_flocking_amd.learners.core import _ops
 

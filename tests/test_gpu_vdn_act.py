@@ -325,3 +325,11 @@ def test_opcheck_and_overlap_refusal(cuda):
         flock.vdn_act(obs, both[:B], *P, both[1:], act, None, None, None, None, 0.0, 0)
     with pytest.raises(RuntimeError, match="coin and rnd"):
         flock.vdn_act(obs, hid, *P, h, act, None, coin, None, None, 0.3, 0)
+    # hidden rows that are not 16-byte aligned: a base pointer off by one float, a row pitch of 33 floats
+    off = torch.zeros(B * A * 32 + 4, device=cuda)[1:1 + B * A * 32].view(B, A, 32)
+    pitch = torch.zeros(B, A, 33, device=cuda)[:, :, :32]
+    for bad in (off, pitch):
+        with pytest.raises(RuntimeError, match="16-byte aligned"):
+            flock.vdn_act(obs, bad, *P, h, act, None, None, None, None, 0.0, 0)
+        with pytest.raises(RuntimeError, match="16-byte aligned"):
+            flock.vdn_act(obs, hid, *P, bad, act, None, None, None, None, 0.0, 0)
