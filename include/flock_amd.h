@@ -57,7 +57,9 @@ const char* flock_last_error(void);
  * ranges per step), "no_spec" (generic step instantiations), "no_split" (one lane per agent in the split-scan
  * instantiations), "no_cells" (full scans instead of the cell list), "pf" (-1 default / 0 off: the env blocks' L2
  * pull-ahead of a later block's inputs in the shapes compiled with it), "sc_no_spec" (generic shared-critic row
- * kernels at fc 400/300), "sc_event_system_scope" (the learn() pipeline's events as HIP's default system-scope fences
+ * kernels at fc 400/300), "sc_red_legacy" (the four separate fc1 / LN1 reduction families of the shared-critic late
+ * launch instead of the fused 16-column strips at in_dim 4; read when a job or a pipeline is built),
+ * "sc_event_system_scope" (the learn() pipeline's events as HIP's default system-scope fences
  * instead of device-scope releases; read when a pipeline is created), "sc_free_events" (every learn() slot freed by
  * a learner-stream event, as in round 5, instead of on the device for gated single-GPU learns), "rollout_spl" (2 or 4
  * lanes per agent in the uw rollout kernel). The library reads no environment variable for them: flock_set_diag is the only way to

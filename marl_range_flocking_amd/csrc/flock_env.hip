@@ -2059,6 +2059,7 @@ Params base(int E, int N, int k, float box) {
 // C ABI
 
 void flock_sc_diag_no_spec(bool v);       // flock_sc.hip
+void flock_sc_diag_red_legacy(bool v);    // flock_sc.hip
 void flock_sc_diag_event_system(bool v);  // flock_sc.hip
 void flock_sc_diag_free_events(bool v);   // flock_sc.hip
 
@@ -2083,6 +2084,8 @@ int flock_set_diag(const char* name, int value) {
         k.rollout_spl = value;
     else if (!strcmp(name, "sc_no_spec"))
         flock_sc_diag_no_spec(value != 0);
+    else if (!strcmp(name, "sc_red_legacy"))
+        flock_sc_diag_red_legacy(value != 0);
     else if (!strcmp(name, "sc_event_system_scope"))
         flock_sc_diag_event_system(value != 0);
     else if (!strcmp(name, "sc_free_events"))

@@ -99,7 +99,7 @@ struct Ws {
     float *TH1, *NH1, *XH1, *RS1, *H1;     // fc1 outputs: target actor(s'), critic(s'), critic(s) xhat/rstd/h
     float* Z2;                             // [3][B][H2] fc2 pre-LN: target actor(s'), critic(s'), critic(s)
     float *XH2, *RS2, *HQ, *DZA, *DY2, *DZ2, *DQ, *LOSS;
-    float *DY1, *DXH1, *PS1;               // LN1 backward: dy, dxh = dy g1, row sums per dH tile [B][tiles][2]
+    float *DY1, *DXH1, *PS1;               // LN1 backward: dy, dxh = dy g1, row sums per dH tile [tiles][B][2]
     float *AXH1, *ARS1, *AH1, *CH1;        // actor phase fc1: actor xhat/rstd/h, updated critic h
     float* Z2b;                            // [2][B][H2] actor fc2, critic fc2
     float *AXH2, *ARS2, *AH2, *DM, *ADY2, *ADZ2, *ALOSS;
@@ -659,9 +659,14 @@ __device__ unsigned long long g_scmark[4096][8];
 #define SC_MARK(MK, i)                                                                           \
     if (MK && threadIdx.x == 0 && blockIdx.x + gridDim.x * blockIdx.y < 4096)                   \
         g_scmark[blockIdx.x + gridDim.x * blockIdx.y][i] = __builtin_amdgcn_s_memrealtime();
+// phase marks of the late launch's reduction blocks (0 entry, 1 row statistics done, 2 last row batch consumed, 3 stored)
+__device__ unsigned long long g_sclate[4096][4];
+#define SC_LMARK(MK, i) \
+    if (MK && threadIdx.x == 0 && blockIdx.x < 4096) g_sclate[blockIdx.x][i] = __builtin_amdgcn_s_memrealtime();
 #else
 #define SC_PROF(k)
 #define SC_MARK(MK, i)
+#define SC_LMARK(MK, i)
 #endif
 // -DFLOCK_SC_PRIO=n (A/B builds only, tools/build_variant_sc.sh): the round kernels' waves raise their issue priority
 // to n (s_setprio) over co-resident env waves
@@ -1054,7 +1059,8 @@ __global__ __launch_bounds__(256) void sc_gemm(GemmBatch gb) {
 //        and the reductions whose inputs the row kernels already wrote (fc2.bias, LN2, heads, loss): gradients only.
 //   late (sc_grad_adam): the fc1 / LN1 reductions, with dz = rstd (dxh - mean(dxh) - xhat mean(dxh xhat)) formed on
 //        the fly from those row sums (no LN1-backward launch), Adam inline; Adam of the parameters whose gradients
-//        the bwd launch wrote; the step counter; the critic's self soft update when it has no view.
+//        the bwd launch wrote; the step counter; the critic's self soft update when it has no view. At in_dim 4 the
+//        fc1 / LN1 reductions are fused 16-column strips (fused_block) instead of the modes 4 / 5 / 1 / 0 below.
 // Reductions: red[q] (the last q with red[q].blk0 <= block) over the B rows, 16 elements per block (16 row groups):
 //   mode 0: g[o] = sum_b D[b, o]         (biases, LayerNorm beta)
 //   mode 1: g[o] = sum_b D[b, o] X[b, o] (LayerNorm gamma)
@@ -1080,13 +1086,46 @@ constexpr int kMaxRedBlocks = 4096;
 
 // LN1 row statistics for modes 4 / 5, from the bwd launch's per-tile row sums
 struct DzArgs {
-    const float *XH, *RS, *PS;  // xhat [B][F], rstd [B], row sums [B][ntn][2]
+    const float *XH, *RS, *PS;  // xhat [B][F], rstd [B], row sums [ntn][B][2] (tile-major)
     int F, ntn;
 };
+
+// ln_backward's dz of one element, from the row's rstd and means (mean(dxh), mean(dxh xhat)); the one expression of
+// both the four-family and the fused reduction blocks
+__device__ __forceinline__ float ln1_dz(float rs, float dxh, float xh, float m1, float m2) {
+    return rs * (dxh - m1 - xh * m2);
+}
+
+// mean(dxh), mean(dxh xhat) of every row into mst [B][2] (LDS): the row's tile partial sums added in tile order.
+// Tile-major partials: consecutive threads (rows) read consecutive float2. No barrier here.
+__device__ __forceinline__ void ln1_row_stats(const DzArgs& dz, int B, float* mst) {
+    const float2* ps = reinterpret_cast<const float2*>(dz.PS);
+    for (int r = threadIdx.x; r < B; r += 256) {
+        float s1 = 0.0f, s2 = 0.0f;
+        // the row's tile sums in batches of 16 independent loads (one memory round trip per batch; a plain loop
+        // waited for each load in turn: 13 round trips at fc1 = 400), added in tile order
+        constexpr int kPB = 16;
+        for (int t0 = 0; t0 < dz.ntn; t0 += kPB) {
+            float2 v[kPB];
+#pragma unroll
+            for (int u = 0; u < kPB; ++u)
+                v[u] = t0 + u < dz.ntn ? ps[(int64_t)(t0 + u) * B + r] : make_float2(0.0f, 0.0f);
+#pragma unroll
+            for (int u = 0; u < kPB; ++u)
+                if (t0 + u < dz.ntn) {
+                    s1 += v[u].x;
+                    s2 += v[u].y;
+                }
+        }
+        mst[2 * r] = s1 / (float)dz.F;
+        mst[2 * r + 1] = s2 / (float)dz.F;
+    }
+}
 
 // One block's reduction: the kRedElems-element slice of rp for block b (thread el = tid % kRedElems, row group
 // q = tid / kRedElems);
 // returns the sum in threads q == 0 (0 elsewhere). part: 256 floats of LDS; mst: [B][2] LDS (modes 4 / 5)
+template <int MK = 0>
 __device__ __forceinline__ float red_block(const RedP& rp, int b, int B, const DzArgs& dz, float* part, float* mst,
                                            int& e_out, bool& live_out) {
     const int tid = threadIdx.x;
@@ -1112,31 +1151,13 @@ __device__ __forceinline__ float red_block(const RedP& rp, int b, int B, const D
             rs[k] = (in && dzm) ? dz.RS[r] : 0.0f;
         }
     };
+    SC_LMARK(MK, 0)
     load(q);  // the first batch is in flight while the LN1 row statistics are formed
     if (dzm) {  // mean(dxh), mean(dxh xhat) of every row: its tiles' partial sums in a fixed order
-        for (int r = tid; r < B; r += 256) {
-            const float2* ps = reinterpret_cast<const float2*>(dz.PS + (int64_t)r * 2 * dz.ntn);
-            float s1 = 0.0f, s2 = 0.0f;
-            // the row's tile sums in batches of 16 independent loads (one memory round trip per batch; a plain loop
-            // waited for each load in turn: 13 round trips at fc1 = 400), added in tile order
-            constexpr int kPB = 16;
-            for (int t0 = 0; t0 < dz.ntn; t0 += kPB) {
-                float2 v[kPB];
-#pragma unroll
-                for (int u = 0; u < kPB; ++u)
-                    v[u] = t0 + u < dz.ntn ? ps[t0 + u] : make_float2(0.0f, 0.0f);
-#pragma unroll
-                for (int u = 0; u < kPB; ++u)
-                    if (t0 + u < dz.ntn) {
-                        s1 += v[u].x;
-                        s2 += v[u].y;
-                    }
-            }
-            mst[2 * r] = s1 / (float)dz.F;
-            mst[2 * r + 1] = s2 / (float)dz.F;
-        }
+        ln1_row_stats(dz, B, mst);
         __syncthreads();
     }
+    SC_LMARK(MK, 1)
     float acc = 0.0f;
     for (int r0 = q; r0 < B; r0 += kRedGroups * kRB) {
         if (r0 != q) load(r0);
@@ -1144,12 +1165,13 @@ __device__ __forceinline__ float red_block(const RedP& rp, int b, int B, const D
 #pragma unroll
             for (int k = 0; k < kRB; ++k) {
                 const int r = min(r0 + kRedGroups * k, B - 1);
-                dv[k] = rs[k] * (dv[k] - mst[2 * r] - xh[k] * mst[2 * r + 1]);  // ln_backward's dz
+                dv[k] = ln1_dz(rs[k], dv[k], xh[k], mst[2 * r], mst[2 * r + 1]);
             }
         }
 #pragma unroll
         for (int k = 0; k < kRB; ++k) acc = prod ? fmaf(dv[k], xv[k], acc) : acc + dv[k];
     }
+    SC_LMARK(MK, 2)
     part[q * kRedElems + el] = acc;
     __syncthreads();
     float gsum = 0.0f;
@@ -1234,8 +1256,8 @@ __device__ __forceinline__ void bwd_body(const BwdJob& j, int bx) {
             for (int q = 0; q < 4; ++q) {
                 const int m = tm * kT + 8 * wv + 4 * (l >> 5) + q;
                 if (m < g.M) {
-                    j.PS1[((int64_t)m * j.ntn + tn) * 2] = s1[q];
-                    j.PS1[((int64_t)m * j.ntn + tn) * 2 + 1] = s2[q];
+                    j.PS1[((int64_t)tn * j.B + m) * 2] = s1[q];  // tile-major: the late launch reads rows coalesced
+                    j.PS1[((int64_t)tn * j.B + m) * 2 + 1] = s2[q];
                 }
             }
         }
@@ -1290,6 +1312,10 @@ struct GradAdam {
     int nred, nblk, B, do_adam;
     RedP red[kMaxRed];
     DzArgs dz;
+    // fused fc1 / LN1 family (fused_in != 0: the nblk reduction blocks are 16-column strips, fused_block; nred = 0)
+    int fused_in;
+    const float *fDXH, *fDY, *fS;       // dxh, dy [B][dz.F]; fc1 input rows [B][fused_in]
+    int64_t fW1, fb1, fg1, fbe1;        // parameter offsets of fc1.weight / fc1.bias / LN1 gamma / LN1 beta
     int64_t adam_lo, adam_n;  // Adam-only region (gradients written by the bwd launch), relative to the agent base
     int adam_blocks;
     float *p, *grad, *m, *v;
@@ -1342,6 +1368,84 @@ __device__ __forceinline__ void adam_store(const GradAdam& ga, int64_t i, AdamSt
     if (soft && ga.target) ga.target[i] = ga.tau * pn + ga.one_minus_tau * s.t;  // soft_update_kernel mode 1
 }
 
+// Fused fc1 / LN1 reduction block: strip b = feature columns [16 b, 16 b + 16) over all rows in ONE sweep of dxh, dy
+// and xhat (64-B row segments), 256 threads = 16 columns (el) x 16 row groups (q; rows q, q + 16, ... in batches of
+// FLOCK_RED_RB, as red_block). Per column 3 + IN outputs: fc1.weight[o][i] = sum dz S[., i], fc1.bias = sum dz,
+// gamma1 = sum dy xhat, beta1 = sum dy. Each output's chain over a group's rows (rows past B as zeros) and the sum
+// over the groups in group order are those of red_block's modes 4 / 5 / 1 / 0: bitwise the four families' values.
+// Output t of the strip (thread t sums it over the groups and runs its Adam): t < 16 IN: fc1.weight element
+// 16 IN b + t; then 16 each of fc1.bias, gamma1, beta1. smem: (3 + IN) x kFusedPitch partials, then mst [B][2].
+constexpr int kFusedPitch = 256 + 8;  // the IN weight planes of a column on different LDS banks
+template <int IN>
+__device__ __forceinline__ void fused_block(const GradAdam& ga, int b, int64_t base, int64_t gbase, float* smem,
+                                            const float* sh, const int& sh_soft) {
+    static_assert(IN == 4, "one 16-B load of the row's inputs");
+    constexpr int kNV = IN + 3, kOut = kRedElems * kNV, kRB = FLOCK_RED_RB;
+    const int tid = threadIdx.x, B = ga.B, F = ga.dz.F;
+    const int el = tid & (kRedElems - 1), q = tid / kRedElems;
+    const int o = b * kRedElems + el;
+    const bool live = o < F;
+    float* mst = smem + kNV * kFusedPitch;
+    SC_LMARK(1, 0)
+    // this thread's output: plane v of column c
+    const int v = tid < kRedElems * IN ? tid % IN : IN + (tid - kRedElems * IN) / kRedElems;
+    const int c = tid < kRedElems * IN ? tid / IN : (tid - kRedElems * IN) % kRedElems;
+    const int oc = b * kRedElems + c;
+    const bool wr = tid < kOut && oc < F;
+    const int64_t poff = v < IN ? ga.fW1 + (int64_t)oc * IN + v : (v == IN ? ga.fb1 : v == IN + 1 ? ga.fg1 : ga.fbe1) + oc;
+    const AdamState st = (wr && ga.do_adam) ? adam_load(ga, base + poff) : AdamState{0.f, 0.f, 0.f, 0.f};
+    float dxh[kRB], dy[kRB], xh[kRB], rs[kRB];
+    float4 sv[kRB];
+    auto load = [&](int r0) {
+#pragma unroll
+        for (int k = 0; k < kRB; ++k) {
+            const int r = r0 + kRedGroups * k;
+            const bool in = live && r < B;
+            dxh[k] = in ? ga.fDXH[(int64_t)r * F + o] : 0.0f;
+            dy[k] = in ? ga.fDY[(int64_t)r * F + o] : 0.0f;
+            xh[k] = in ? ga.dz.XH[(int64_t)r * F + o] : 0.0f;
+            rs[k] = in ? ga.dz.RS[r] : 0.0f;
+            sv[k] = in ? *reinterpret_cast<const float4*>(ga.fS + (int64_t)r * IN) : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+    };
+    load(q);  // the first batch is in flight while the LN1 row statistics are formed
+    ln1_row_stats(ga.dz, B, mst);
+    __syncthreads();
+    SC_LMARK(1, 1)
+    float aw[IN] = {0.0f, 0.0f, 0.0f, 0.0f}, ab = 0.0f, ag = 0.0f, abe = 0.0f;
+    for (int r0 = q; r0 < B; r0 += kRedGroups * kRB) {
+        if (r0 != q) load(r0);
+#pragma unroll
+        for (int k = 0; k < kRB; ++k) {
+            const int r = min(r0 + kRedGroups * k, B - 1);
+            const float dz = ln1_dz(rs[k], dxh[k], xh[k], mst[2 * r], mst[2 * r + 1]);
+            aw[0] = fmaf(dz, sv[k].x, aw[0]);
+            aw[1] = fmaf(dz, sv[k].y, aw[1]);
+            aw[2] = fmaf(dz, sv[k].z, aw[2]);
+            aw[3] = fmaf(dz, sv[k].w, aw[3]);
+            ab = ab + dz;
+            ag = fmaf(dy[k], xh[k], ag);
+            abe = abe + dy[k];
+        }
+    }
+    SC_LMARK(1, 2)
+    const int slot = q * kRedElems + el;
+#pragma unroll
+    for (int i = 0; i < IN; ++i) smem[i * kFusedPitch + slot] = aw[i];
+    smem[IN * kFusedPitch + slot] = ab;
+    smem[(IN + 1) * kFusedPitch + slot] = ag;
+    smem[(IN + 2) * kFusedPitch + slot] = abe;
+    __syncthreads();
+    if (wr) {
+        float gsum = 0.0f;
+#pragma unroll
+        for (int k = 0; k < kRedGroups; ++k) gsum += smem[v * kFusedPitch + k * kRedElems + c];
+        ga.grad[gbase + poff] = gsum;
+        if (ga.do_adam) adam_store(ga, base + poff, st, gsum, sh[0], sh[1], sh_soft != 0);
+    }
+    SC_LMARK(1, 3)
+}
+
 // one job's blocks of the late launch: [0, nblk) reductions, [nblk, + adam_blocks) Adam of the bwd launch's
 // gradients, then soft_blocks self soft update blocks
 __device__ __forceinline__ void grad_adam_body(const GradAdam& ga, int bx, int nb) {
@@ -1352,17 +1456,24 @@ __device__ __forceinline__ void grad_adam_body(const GradAdam& ga, int bx, int n
     const int tid = threadIdx.x;
     const int64_t agent = ga.rel ? agent_at(ga.agent, ga.agent_v) : 0;
     const int64_t base = ga.rel * agent, gbase = ga.grad_rel * agent;
-    if (tid == 0) {
+    const int adam0 = ga.nblk, soft0 = ga.nblk + ga.adam_blocks;
+    // the soft flag and the bias corrections for the block. The two double pow cost thread 0's wave ~2 us in front of
+    // every block's first barrier (phase marks, profiles/fused_red/): lanes 0 and 1 take one each
+    if (tid < 2) {
         const int64_t step0 = ga.do_adam ? ga.step[agent] : 0;
-        const int64_t count = ga.soft_count ? ga.soft_count[agent_at(ga.agent, ga.agent_v)] : step0;
-        sh_soft = ga.do_adam && ga.soft_rate > 0 && (count % ga.soft_rate) == 0;  // this learn's count
+        if (tid == 0) {
+            const int64_t count = ga.soft_count ? ga.soft_count[agent_at(ga.agent, ga.agent_v)] : step0;
+            sh_soft = ga.do_adam && ga.soft_rate > 0 && (count % ga.soft_rate) == 0;  // this learn's count
+        }
         if (ga.do_adam) {
             const double st = (double)(step0 + 1);
-            sh[0] = (float)(-(double)ga.lr / (1.0 - pow((double)ga.b1, st)));
-            sh[1] = (float)sqrt(1.0 - pow((double)ga.b2, st));
+            const double pw = pow(tid == 0 ? (double)ga.b1 : (double)ga.b2, st);
+            if (tid == 0)
+                sh[0] = (float)(-(double)ga.lr / (1.0 - pw));
+            else
+                sh[1] = (float)sqrt(1.0 - pw);
         }
     }
-    const int adam0 = ga.nblk, soft0 = ga.nblk + ga.adam_blocks;
     if (bx >= soft0) {  // critic self soft update blocks (after its Adam step)
         __syncthreads();
         if (sh_soft && ga.self_soft) {
@@ -1395,6 +1506,8 @@ __device__ __forceinline__ void grad_adam_body(const GradAdam& ga, int bx, int n
             const int64_t e = e0 + q * 256 + tid;
             if (e < end) adam_store(ga, base + e, st[q], ga.grad_scale ? gi[q] * gs : gi[q], sh[0], sh[1], sh_soft != 0);
         }
+    } else if (ga.fused_in == 4) {  // fused fc1 / LN1 strips (late_common)
+        fused_block<4>(ga, bx, base, gbase, smem, sh, sh_soft);
     } else {
         const int b = bx;
         int q0 = 0;  // descriptor of this block: a wave-uniform search over <= kMaxRed scalars
@@ -1406,11 +1519,12 @@ __device__ __forceinline__ void grad_adam_body(const GradAdam& ga, int bx, int n
         const AdamState st = ad ? adam_load(ga, base + rp.off + e1) : AdamState{0.f, 0.f, 0.f, 0.f};
         int e;
         bool wr;
-        const float gsum = red_block(rp, b, ga.B, ga.dz, smem, smem + 256, e, wr);
+        const float gsum = red_block<1>(rp, b, ga.B, ga.dz, smem, smem + 256, e, wr);
         if (wr) {
             ga.grad[gbase + rp.off + e] = gsum;
             if (ga.do_adam) adam_store(ga, base + rp.off + e, st, gsum, sh[0], sh[1], sh_soft != 0);
         }
+        SC_LMARK(1, 3)
     }
     // the last block to arrive advances the step counter. No fence: every block's thread 0 consumed its load of
     // *step (the bias corrections) before its relaxed atomic add, and the increment only has to be visible to the
@@ -1533,7 +1647,9 @@ void add_red(J& ga, const float* D, int ldd, const float* X, int ldx, int mode, 
     r.blk0 = ga.nblk;
     ga.nblk += (n + kRedElems - 1) / kRedElems;
 }
-size_t red_lds(int B) { return (size_t)(256 + 2 * B) * sizeof(float); }  // part + LN1 row statistics
+// the late launch's reduction blocks: the fused strips' partials (the four families' 256 fit in them) + LN1 row
+// statistics
+size_t red_lds(int B) { return (size_t)(7 * kFusedPitch + 2 * B) * sizeof(float); }
 size_t bwd_lds(const BwdJob& j) {
     const size_t a = gemm_lds_bytes(j.dh.K, j.dh.kchunk), b = gemm_lds_bytes(j.dw.K, j.dw.kchunk);
     const size_t r = 256 * sizeof(float);
@@ -1635,6 +1751,11 @@ void bwd_common(Job& j, const float* W2, int64_t rel_w2, const int64_t* agent, c
     bw.grad = grad; bw.rel = rel; bw.grad_rel = rel; bw.agent = agent; bw.agent_v = -1; bw.loss = loss;
 }
 
+// flock_set_diag("sc_red_legacy", 1): the four separate fc1 / LN1 reduction families (modes 4, 5, 1, 0) at every
+// in_dim, instead of the fused strips at in_dim 4 (bitwise the same results; tests and A/B timing). Read when a job is
+// built (a pipeline's jobs: when it is created).
+bool g_sc_red_legacy = false;
+
 // the late launch's job: fc1 / LN1 reductions (+ Adam), Adam of [W2, total)
 void late_common(Job& j, const FlockScUpdate* u, const float* DXH1, const float* DY1, const float* XH1,
                  const float* RS1, const float* PS1, int64_t W1, int64_t b1, int64_t g1, int64_t be1, int64_t W2,
@@ -1645,10 +1766,17 @@ void late_common(Job& j, const FlockScUpdate* u, const float* DXH1, const float*
     ga.nblk = 0;
     ga.B = j.B;
     ga.do_adam = u->do_adam;
-    add_red(ga, DXH1, H1, j.w.S, in, 4, in, H1 * in, W1);
-    add_red(ga, DXH1, H1, nullptr, 0, 5, 1, H1, b1);
-    add_red(ga, DY1, H1, XH1, H1, 1, 1, H1, g1);
-    add_red(ga, DY1, H1, nullptr, 0, 0, 1, H1, be1);
+    ga.fused_in = (!g_sc_red_legacy && in == 4) ? in : 0;
+    ga.fDXH = DXH1; ga.fDY = DY1; ga.fS = j.w.S;
+    ga.fW1 = W1; ga.fb1 = b1; ga.fg1 = g1; ga.fbe1 = be1;
+    if (ga.fused_in) {  // one block per 16 feature columns: all 3 + in outputs of a column from one sweep
+        ga.nblk = (H1 + kRedElems - 1) / kRedElems;
+    } else {
+        add_red(ga, DXH1, H1, j.w.S, in, 4, in, H1 * in, W1);
+        add_red(ga, DXH1, H1, nullptr, 0, 5, 1, H1, b1);
+        add_red(ga, DY1, H1, XH1, H1, 1, 1, H1, g1);
+        add_red(ga, DY1, H1, nullptr, 0, 0, 1, H1, be1);
+    }
     ga.dz = DzArgs{XH1, RS1, PS1, H1, j.bw.ntn};
     ga.adam_lo = W2;
     ga.adam_n = total - W2;
@@ -1973,6 +2101,8 @@ __global__ __launch_bounds__(256) void sc_prep_snapshot_gate(int B, int64_t rows
 
 // the "sc_no_spec" diagnostics knob of flock_set_diag (flock_env.hip)
 void flock_sc_diag_no_spec(bool v) { g_sc_no_spec = v; }
+// the "sc_red_legacy" knob (late_common)
+void flock_sc_diag_red_legacy(bool v) { g_sc_red_legacy = v; }
 void flock_sc_diag_event_system(bool v);  // below (the pipeline's event flags)
 
 int round_adam(void* stream, const FlockScUpdate* critic_u, const FlockScUpdate* actor_u, const float* grad_scale,
@@ -2048,6 +2178,7 @@ int round_adam(void* stream, const FlockScUpdate* critic_u, const FlockScUpdate*
         GradAdam& g = *js[i];
         g.nred = 0;
         g.nblk = 0;
+        g.fused_in = 0;
         g.adam_lo = 0;
         g.grad_scale = grad_scale;
     }
@@ -2601,6 +2732,9 @@ int flock_sc_prof_read(unsigned long long* host) {
 }
 int flock_sc_mark_read(unsigned long long* host) {
     return hipMemcpyFromSymbol(host, HIP_SYMBOL(g_scmark), sizeof(g_scmark)) != hipSuccess;
+}
+int flock_sc_late_mark_read(unsigned long long* host) {
+    return hipMemcpyFromSymbol(host, HIP_SYMBOL(g_sclate), sizeof(g_sclate)) != hipSuccess;
 }
 #endif
 

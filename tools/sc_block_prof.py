@@ -26,9 +26,10 @@ def build():
     obj = os.path.join(BUILD, "flock_sc_prof.o")
     subprocess.check_call([hipcc()] + HIPCC_FLAGS + ["-DFLOCK_SC_PROF", "-c", "-I", INCLUDE, "-o", obj,
                                                      os.path.join(CSRC, "flock_sc.hip")])
-    subprocess.check_call([hipcc()] + HIPCC_FLAGS + ["-shared", "-o", SO, os.path.join(BUILD, "flock_env.hip.o"),
-                                                     os.path.join(BUILD, "flock_learn.hip.o"),
-                                                     os.path.join(BUILD, "flock_act.hip.o"), obj])
+    from marl_range_flocking_amd.build import sources
+
+    others = [os.path.join(BUILD, os.path.basename(f) + ".o") for f in sources() if not f.endswith("flock_sc.hip")]
+    subprocess.check_call([hipcc()] + HIPCC_FLAGS + ["-shared", "-o", SO] + others + [obj])
     print(SO)
 
 
@@ -97,6 +98,23 @@ def run(corun, learns):
             rel = (m - t[k, idx, 0][:, None]) / 100.0
             print("    gemm phase marks (us from block start, p50 / p90): " + ", ".join(
                 f"{n} {np.percentile(rel[:, i], 50):.2f}/{np.percentile(rel[:, i], 90):.2f}" for i, n in enumerate(names)))
+        if name == "grad_adam" and hasattr(lib, "flock_sc_late_mark_read"):
+            # phase marks of the late launch's reduction blocks (SC_LMARK): per job, its reduction blocks' marks from
+            # the block's start and the blocks' end from the launch's first block
+            mk = (ctypes.c_ulonglong * (4096 * 4))()
+            lib.flock_sc_late_mark_read.argtypes = [ctypes.c_void_p]
+            assert lib.flock_sc_late_mark_read(mk) == 0
+            m = np.frombuffer(mk, dtype=np.uint64).reshape(4096, 4).astype(np.int64)[idx]
+            red = m[:, 0] >= s.min()  # blocks that wrote an entry mark in this launch: the reduction blocks
+            names = ["entry", "stats done", "last batch consumed", "stored"]
+            rel = (m[red] - t[k, idx[red], 0][:, None]) / 100.0
+            print(f"    late reduction blocks {red.sum()} of {len(idx)}; marks (us from block start, p50 / p90 / max): "
+                  + ", ".join(f"{n} {np.percentile(rel[:, i], 50):.2f}/{np.percentile(rel[:, i], 90):.2f}/"
+                              f"{rel[:, i].max():.2f}" for i, n in enumerate(names)))
+            endr = (t[k, idx[red], 1] - s.min()) / 100.0
+            endo = (t[k, idx[~red], 1] - s.min()) / 100.0
+            print(f"    end from the launch's first block start: reduction blocks p50 {np.median(endr):.1f} max "
+                  f"{endr.max():.1f}; Adam-only blocks p50 {np.median(endo):.1f} max {endo.max():.1f}")
         # block-index ranges (16 equal slices): median start offset and median duration
         for q in np.array_split(np.arange(len(idx)), min(16, len(idx))):
             if len(q) == 0:
@@ -111,5 +129,15 @@ if __name__ == "__main__":
     ap.add_argument("--build", action="store_true")
     ap.add_argument("--corun", action="store_true")
     ap.add_argument("--learns", type=int, default=40)
+    ap.add_argument("--diag-knob", action="append", default=[], metavar="NAME=VALUE", help="flock_set_diag first")
     args = ap.parse_args()
-    build() if args.build else run(args.corun, args.learns)
+    if args.build:
+        build()
+    else:
+        for kv in args.diag_knob:
+            sys.path.insert(0, ROOT)
+            from marl_range_flocking_amd import _native
+
+            name, value = kv.split("=")
+            assert _native.lib().flock_set_diag(name.encode(), int(value)) == 0, kv
+        run(args.corun, args.learns)
