@@ -674,12 +674,18 @@ int launch_act(hipStream_t st, const ActArgs& a, size_t lds, bool stage) {
     return launched();
 }
 
+// LDS bytes of a sc_act16_kernel block with nt 16-column tiles (in_dim 4): fc1 rows and (b1, g1, be1, 0), the
+// observation rows, the LayerNorm-1 statistics, fc2's row parameters and the staged chunk
+size_t act16_lds(int H1, int nt) {
+    return sizeof(float) * ((size_t)H1 * 4 + 4 * (size_t)H1 + 64 * 4 + 2 * 64 + 5 * 16 * (size_t)nt +
+                            (size_t)16 * nt * kBP16);
+}
+
 // the 16 x 16 kernel (NT 16-column tiles; in_dim 4, the LDS staging path, 64-row blocks)
 template <int NT>
 int launch_act16(hipStream_t st, ActArgs a) {
     a.tiles = (int)((a.rows + 63) / 64);
-    const size_t lds = sizeof(float) * ((size_t)a.H1 * 4 + 4 * (size_t)a.H1 + 64 * 4 + 2 * 64 +
-                                        5 * 16 * NT + (size_t)16 * NT * kBP16);
+    const size_t lds = act16_lds(a.H1, NT);
     if (lds > 64 * 1024) return fail(-5, "flock_sc_act: fc1 too wide for the LDS staging");
     hipLaunchKernelGGL((sc_act16_kernel<NT, 4>), dim3(a.A * a.tiles), dim3(256), lds, st, a);
     return launched();
@@ -698,7 +704,8 @@ int launch_act_tm(hipStream_t st, ActArgs a, int inp, bool stage, int tm) {
 extern "C" int flock_sc_act(void* stream, int64_t rows, int n_agents, int in_dim, int fc1, int fc2, const float* obs,
                             const float* actors, int64_t actor_stride, float* actions, float* ou_state,
                             const float* noise, float theta, float dt, float sigma_sqrt_dt) {
-    if (!obs || !actors || !actions || (ou_state && !noise))
+    // (no rows: nothing is read or written, and an empty tensor's data pointer is NULL)
+    if (rows != 0 && (!obs || !actors || !actions || (ou_state && !noise)))
         return fail(-3, "flock_sc_act: NULL argument");
     if (rows < 0 || n_agents < 1 || in_dim < 1 || in_dim > 16 || fc1 < 8 || (fc1 & 7) || fc2 < 1 || fc2 > 320)
         return fail(-5, "flock_sc_act: needs 1 <= in_dim <= 16, fc1 a multiple of 8, 1 <= fc2 <= 320");
@@ -729,7 +736,9 @@ extern "C" int flock_sc_act(void* stream, int64_t rows, int n_agents, int in_dim
     hipStream_t st = (hipStream_t)stream;
     const int nt = (fc2 + 63) / 64;
     constexpr bool stage = true;  // fc2.weight through LDS (launch_act falls back to global reads past 64 KB of LDS)
-    if (in_dim == 4) {  // the 16 x 16 kernel at the widths it is instantiated for
+    // the 16 x 16 kernel at the widths it is instantiated for; an fc1 whose block does not fit its LDS there goes on to
+    // the 32 x 32 kernel, whose block is smaller (no fc2 row parameters in LDS, fc2.weight read from global memory)
+    if (in_dim == 4 && act16_lds(fc1, (fc2 + 15) / 16) <= 64 * 1024) {
         switch ((fc2 + 15) / 16) {  // the widths with an instantiation; others take the 32 x 32 kernel
             case 7: return launch_act16<7>(st, a);
             case 19: return launch_act16<19>(st, a);

@@ -276,9 +276,17 @@ class SharedCriticLearner:
         return {n: fp.view(fp.target if target else fp.data, n) for n in fp.shapes}
 
     def fused_act_ok(self):
-        """The widths flock_sc_act handles (the reference's 400 / 300 / 2 among them)."""
-        return (self.n_actions == 2 and 1 <= self.input_dim <= 16 and self.fc1 % 8 == 0 and self.fc1 >= 8
-                and 1 <= self.fc2 <= 320)
+        """The widths flock_sc_act handles (the reference's 400 / 300 / 2 among them): its argument check and the LDS
+        of its widest-reaching block. Mirrors csrc/flock_act.hip launch_act_tm: the 32 x 32 kernel's block holds
+        fc1 rows [fc1][inp] (inp = in_dim rounded up to a multiple of 4), (b1, g1, be1, 0) [fc1], the observation rows
+        [64][inp] and 8 x 64 floats of statistics in at most 64 KB (fc1 <= 1952 at in_dim <= 4, 736 at in_dim 13-16);
+        fc2.weight is read from global memory where its staged chunk no longer fits (launch_act), and an in_dim-4
+        width the 16 x 16 kernel cannot hold goes to this kernel (flock_sc_act), so this one bound decides."""
+        if not (self.n_actions == 2 and 1 <= self.input_dim <= 16 and self.fc1 % 8 == 0 and self.fc1 >= 8
+                and 1 <= self.fc2 <= 320):
+            return False
+        inp = (self.input_dim + 3) & ~3
+        return 4 * (self.fc1 * inp + 4 * self.fc1 + 64 * inp + 8 * 64) <= 64 * 1024
 
     @torch.no_grad()
     def choose_action(self, obs, noise=True, fused=None):
